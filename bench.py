@@ -11,6 +11,8 @@ cube vertex it holds).  Strong scaling: the C96 problem is fixed as N grows.
 
     python bench.py                              # 1 GPU
     python bench.py --gpus 8                     # spawns 8 ranks (torch.distributed.run)
+    python bench.py --full                       # + the checks and diagnostics below
+    python bench.py --dump-outputs DIR           # + the final state as DIR/<field>.npy
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -21,12 +23,20 @@ Rank 0 prints one JSON line.  Order of events on every rank:
   2. ``prepare(K)``: record the graph(s) ``run(K)`` replays and replay them
      once on a scratch copy of the state (instantiate/upload outside timing);
   3. W warmup steps;
-  4. N > 1: the warmup state is compared with a one-GPU run of the same W
-     steps (must be bit-identical) BEFORE timing; a mismatch or a poll
-     timeout falls back to RCCL from a fresh state, a second mismatch aborts;
+  4. ``--full``, N > 1: the warmup state is compared with a one-GPU run of
+     the same W steps (must be bit-identical) BEFORE timing; a mismatch or a
+     poll timeout falls back to RCCL from a fresh state, a second mismatch
+     aborts;
   5. barrier + synchronize, exactly K steps, synchronize + barrier; the time
      is the max over ranks; the runner's counters must show K graph-replayed
-     steps and no eager ones where a graph path was chosen.
+     steps and no eager ones where a graph path was chosen (the fused step
+     advances two steps per period: an odd K ends with one single-step launch
+     of the same kernel, counted as the one eager step that is allowed);
+  6. ``--dump-outputs DIR``: the state after the last timed step, one
+     ``DIR/<field>.npy`` of shape [6, N, N] per prognostic field;
+  7. ``--full`` only: the final state against a one-GPU run (N > 1), the
+     finiteness of the state and the mass diagnostic.  A plain run leaves
+     those keys of the JSON line null.
 """
 from __future__ import annotations
 
@@ -91,7 +101,15 @@ def parse(argv=None):
                     help="diagnostics: time R more regions of --steps steps after the measured one "
                          "(reported as repeat_ms_per_step; the state then has advanced further)")
     ap.add_argument("--no-verify", action="store_true",
-                    help="N > 1: skip the bitwise comparisons with a one-GPU run")
+                    help="--full, N > 1: skip the bitwise comparisons with a one-GPU run")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: N > 1 the bitwise comparisons with a one-GPU "
+                         "run (before and after timing), the finiteness check and the mass diagnostic of the "
+                         "final state")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the state they computed as DIR/<field>.npy "
+                         "([6, N, N] per field in the run's precision; above 64 MB in all, a fixed seeded "
+                         "sample of each field)")
     return ap.parse_args(argv)
 
 
@@ -223,6 +241,24 @@ def single_rank_reference(a, phys_factory, grid, dtype, device, dt, ng, nsteps, 
     return np.stack([ref.global_field(f) for f in range(ref.physics.F)])
 
 
+DUMP_LIMIT = 64 << 20   # bytes --dump-outputs writes at most
+
+
+def dump_outputs(path, fields, names):
+    """Rank 0: ``path/<name>.npy`` per field of ``fields`` [F, ...]; when the
+    whole exceeds DUMP_LIMIT, the same seeded sample of every field's cells."""
+    import numpy as np
+    if fields is None:
+        return
+    os.makedirs(path, exist_ok=True)
+    per = DUMP_LIMIT // (len(fields) * fields.itemsize)
+    pick = None
+    if fields[0].size > per:
+        pick = np.sort(np.random.default_rng(0).choice(fields[0].size, size=per, replace=False))
+    for name, f in zip(names, fields):
+        np.save(os.path.join(path, f"{name}.npy"), f if pick is None else f.reshape(-1)[pick])
+
+
 def main():
     a = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -346,7 +382,10 @@ def main():
                 # costs ~18 us of ramp: 300 steps in one launch 12.05 us/step against 12.09-12.18
                 # in 60-step launches, profiles/r4_spl/)
                 cus = _rank_cus(device)
-                spl = max([k for k in range(2, 513, 2) if a.steps % k == 0], default=1) if fk.plan.nb <= cus else 1
+                # (an odd step count: of the even part, the last step is a single-step launch)
+                even = a.steps - a.steps % 2
+                spl = max([k for k in range(2, 513, 2) if even and even % k == 0], default=1) \
+                    if fk.plan.nb <= cus else 1
             info["steps_per_launch"] = spl
             info["fused_B"] = fk.plan.B
             runner = NativeStepper(eng, use_graph=True, steps_per_graph=spg, fused=fk, steps_per_launch=spl,
@@ -414,6 +453,15 @@ def main():
         dist.all_gather_object(allt, tiles)
         return np.stack([assemble_global(layout, {r: t[f] for r, t in enumerate(allt)}) for f in range(phys.F)])
 
+    def state_fields():
+        """[F, 6, N, N] state of the whole sphere in the run's precision (collective; every rank)."""
+        if world > 1:
+            full = gathered(eng)
+        else:
+            tiles = eng.tiles_view().detach().cpu().numpy()
+            full = np.stack([assemble_global(layout, {0: tiles[f]}) for f in range(phys.F)])
+        return full.astype(np.float64 if dtype == torch.float64 else np.float32) if rank == 0 else None
+
     def diff_vs_1gpu(eng, nsteps):
         """max |multi-rank - one rank| after nsteps (0.0 = bitwise), on every rank."""
         got = gathered(eng)
@@ -436,7 +484,7 @@ def main():
     eng = runner = xg = None
     fallback_reason = None
     warm_diff = None
-    verify = world > 1 and not a.no_verify
+    verify = a.full and world > 1 and not a.no_verify
 
     def attempt(c):
         """(engine, runner, exchange, ok, why) of one transport."""
@@ -500,6 +548,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs:
+        _phase("dump_outputs")
+        dump_outputs(a.dump_outputs, state_fields(), phys.fields)
     # diagnostics only (--repeat R): R more timed regions of the same K steps
     # after the measured one, reported separately (the headline is the first)
     repeats = []
@@ -513,16 +564,22 @@ def main():
         runner.check()
     graph_path = runtime in ("native", "fused") and getattr(runner, "use_graph", False) \
         and not getattr(runner, "_cxx_graph", False)
-    if graph_path and (timed.get("eager_steps", 0) != 0 or timed.get("graph_steps", 0) != a.steps):
+    # the fused step has a period of two steps: the last step of an odd count is one
+    # single-step launch of the same kernel, which the runner counts as eager
+    odd = a.steps % 2 if runtime == "fused" else 0
+    if graph_path and (timed.get("eager_steps", 0) != odd or timed.get("graph_steps", 0) != a.steps - odd):
         raise SystemExit(f"[bench] timed region was not a pure graph replay: {timed}")
-    if getattr(runner, "direct", False) and (timed.get("eager_steps", 0) != 0 or timed.get("direct_steps", 0) != a.steps):
+    if getattr(runner, "direct", False) and (timed.get("eager_steps", 0) != odd
+                                             or timed.get("direct_steps", 0) != a.steps - odd):
         raise SystemExit(f"[bench] timed region was not whole direct fused launches: {timed}")
-    diag = eng.diagnostics()
-    if world > 1:
-        t = torch.tensor([diag.get("mass", 0.0)], dtype=torch.float64, device=cdev)
-        dist.all_reduce(t)
-        diag["mass"] = float(t.item())
-    finite = bool(torch.isfinite(eng.tiles_view()).all().item())
+    diag, finite = {}, None
+    if a.full:
+        diag = eng.diagnostics()
+        if world > 1:
+            t = torch.tensor([diag.get("mass", 0.0)], dtype=torch.float64, device=cdev)
+            dist.all_reduce(t)
+            diag["mass"] = float(t.item())
+        finite = bool(torch.isfinite(eng.tiles_view()).all().item())
     _phase("final_verify")
     final_diff = diff_vs_1gpu(eng, a.warmup + a.steps) if verify else None
     cells = 6 * a.N * a.N

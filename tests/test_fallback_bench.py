@@ -17,7 +17,7 @@ def test_bench_falls_back_to_ipc_when_the_rings_fail():
     env = dict(os.environ, STSP_SHARE_GPU="1", STSP_FAIL_XGMI="1", OMP_NUM_THREADS="1",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--N", "48",
-                        "--tiles-per-edge", "2", "--steps", "4", "--warmup", "2", "--timeout", "150"],
+                        "--tiles-per-edge", "2", "--steps", "4", "--warmup", "2", "--timeout", "150", "--full"],
                        capture_output=True, text=True, timeout=200, env=env, cwd=REPO)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and lines, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])

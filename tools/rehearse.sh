@@ -15,7 +15,7 @@ for row in "${rows[@]}"; do
   n=${row%%:*}
   args=${row#*:}
   i=$((i + 1))
-  STSP_SHARE_GPU=1 timeout -k 10 ${ROW_TIMEOUT:-300} python -u bench.py --gpus $n $args --timeout ${ROW_TIMEOUT:-300} \
+  STSP_SHARE_GPU=1 timeout -k 10 ${ROW_TIMEOUT:-300} python -u bench.py --full --gpus $n $args --timeout ${ROW_TIMEOUT:-300} \
     > $OUT/row$i.log 2>&1 || { echo "row $i failed: $row"; tail -5 $OUT/row$i.log; exit 1; }
   tail -n 1 $OUT/row$i.log > $OUT/row$i.json
   echo "row $i ($n ranks, $args):"; cut -c1-400 $OUT/row$i.json; echo
