@@ -1,6 +1,9 @@
 """Command line:  python -m stsphere <command> ...
 
-    run CONFIG.yaml [--days D | --nsteps K] [--plot]   run the solver
+    run CONFIG.yaml [--days D | --nsteps K] [--plot] [--plot-field NAME]
+                                                       run the solver (NAME: a prognostic field,
+                                                       vorticity, divergence or pv)
+    diag CONFIG.yaml [--restore PATH]                  print the invariants of the (restored) state
     info CONFIG.yaml                                   validate config, print sharding + halo plan
     schedule                                           print the reference 4-stage halo schedule
     roofline                                           slide-19 roofline / TT model for MI355X
@@ -24,6 +27,11 @@ def main(argv=None):
     r.add_argument("--days", type=float)
     r.add_argument("--nsteps", type=int)
     r.add_argument("--plot", action="store_true")
+    r.add_argument("--plot-field", default=None,
+                   help="field of the final plot: a prognostic name, vorticity, divergence or pv (default: the first)")
+    dg = sub.add_parser("diag")
+    dg.add_argument("config")
+    dg.add_argument("--restore", default=None, help="checkpoint to read the state from")
     i = sub.add_parser("info")
     i.add_argument("config")
     sub.add_parser("schedule")
@@ -83,13 +91,33 @@ def main(argv=None):
         for rk in range(L.num_ranks):
             print(L.plan(rk).summary())
         return 0
+    if a.cmd == "diag":
+        if a.restore:
+            s.cfg.io.restore = a.restore
+        s.initialize()
+        inv = s.invariants()                      # collective under SPMD
+        s.close()
+        if s.rank == 0:
+            print(json.dumps(dict(step=s.step_count, time_s=s.time, **inv), default=float))
+        return 0
+    from .models.derived import FIELDS as derived_names
     s.initialize()
+    pf = a.plot_field
+    if pf is not None and pf not in list(s.fields) + list(derived_names):
+        ap.error(f"--plot-field {pf}: choose from {list(s.fields) + list(derived_names)}")
     summary = s.run(nsteps=a.nsteps, days=a.days)
     g = s.gather_global() if a.plot else None     # collective under SPMD
+    dfield = s.derived_field(pf) if a.plot and pf in derived_names else None   # collective under SPMD
     s.close()                                     # collective under SPMD (exchange rings)
     if s.rank == 0:
         print(json.dumps(summary, default=float))
-        if a.plot:
+        if a.plot and pf is not None:
+            from .utils.viz import sphere_plot
+            out = s.cfg.io.output_dir
+            os.makedirs(out, exist_ok=True)
+            arr = dfield if dfield is not None else g[s.fields.index(pf)]
+            print(sphere_plot(arr, s.grid, os.path.join(out, f"{pf}_final.png")))
+        elif a.plot:
             from .utils.viz import history_products, sphere_plot
             out = s.cfg.io.output_dir
             os.makedirs(out, exist_ok=True)

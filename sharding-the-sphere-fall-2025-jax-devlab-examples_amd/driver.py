@@ -33,6 +33,7 @@ import torch
 from .engine import Engine, GraphStepper, VirtualCluster, assemble_global
 from .models.advection import Advection
 from .models.base import limiter_code
+from .models.derived import FIELDS as DERIVED_FIELDS, INVARIANTS
 from .models.diffusion import Diffusion
 from .models.geometry import DAY, EARTH_RADIUS, CubedSphereGrid
 from .models.swe import ShallowWater
@@ -42,6 +43,10 @@ from .parallel.mesh import setup_sharding
 from .utils import checkpoint as ckpt
 from .utils.config import Config, default_case, load_config
 from .utils.history import HistoryWriter, MetricsLogger
+
+
+# invariants the metrics records gain with the shallow-water model
+METRIC_INVARIANTS = ("potential_enstrophy", "circulation", "max_courant")
 
 
 def make_physics(pc) -> Any:
@@ -220,6 +225,17 @@ class Solver:
         self.dt = dt
         self.physics = phys0
         self.fields = list(phys0.fields)
+        hf = c.io.history_fields
+        if hf is not None:
+            unknown = [f for f in hf if f not in self.fields and f not in DERIVED_FIELDS]
+            if not hf:
+                raise ValueError("io.history_fields: an empty list (use null for the prognostic fields)")
+            if unknown:
+                raise ValueError(f"io.history_fields: unknown field(s) {unknown}; choose from "
+                                 f"{self.fields + list(DERIVED_FIELDS)}")
+            if phys0.name != "swe" and any(f in DERIVED_FIELDS for f in hf):
+                raise ValueError(f"io.history_fields: derived fields {list(DERIVED_FIELDS)} need the "
+                                 f"shallow-water model, not {phys0.name!r}")
         self._log(f"Initialized {phys0.name} ({getattr(phys0, 'case', '')}) C{N}, {self.mode} mode, "
                   f"backend={backend}, dtype={c.grid.dtype}, dt={dt:.3f} s, integrator={c.time.integrator}")
         if c.io.initial_condition and not c.io.restore:
@@ -322,8 +338,55 @@ class Solver:
         keys = sorted(vals)
         t = torch.tensor([vals[k] for k in keys], dtype=torch.float64,
                          device=self.device if self.device.type == "cuda" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.SUM if op == "sum" else dist.ReduceOp.MIN)
+        dist.all_reduce(t, op={"sum": dist.ReduceOp.SUM, "min": dist.ReduceOp.MIN, "max": dist.ReduceOp.MAX}[op])
         return dict(zip(keys, t.tolist()))
+
+    # ---- derived fields (models/derived.py, ops/derived.py) -------------------------
+    def _derived_all(self):
+        """[(fields [3, T, n, n], inv [8])] of every engine of this process.
+        Ranks with remote ghosts exchange first: all engines start, then all
+        finish (the virtual cluster's lockstep)."""
+        if self.physics.name != "swe":
+            raise ValueError(f"derived fields are defined for the shallow-water model, not {self.physics.name!r}")
+        ds = [e.derived_fields for e in self.engines]
+        for d in ds:
+            d.start()
+        for d in ds:
+            d.finish()
+        return [d.compute() for d in ds]
+
+    def derived_field(self, name: str) -> Optional[np.ndarray]:
+        """[6, N, N] of ``vorticity``, ``divergence`` or ``pv`` on rank 0 (None
+        elsewhere), like ``global_field``."""
+        if name not in DERIVED_FIELDS:
+            raise ValueError(f"unknown derived field {name!r}; choose from {list(DERIVED_FIELDS)}")
+        k = DERIVED_FIELDS.index(name)
+        vals = {e.rank: f[k].detach().cpu().double().numpy() for e, (f, _) in zip(self.engines, self._derived_all())}
+        if self.mode == "spmd":
+            import torch.distributed as dist
+            objs = [None] * self.world
+            dist.all_gather_object(objs, vals)
+            vals = {}
+            for o in objs:
+                vals.update(o)
+            if self.rank != 0:
+                return None
+        return assemble_global(self.layout, vals)
+
+    def invariants(self) -> Dict[str, float]:
+        """mass, energy, potential_enstrophy, circulation, abs_circulation
+        (sums over the sphere) and max_courant (maximum) of the current state."""
+        sums: Dict[str, float] = {}
+        cmax = 0.0
+        for _, inv in self._derived_all():
+            for k, v in zip(INVARIANTS, inv.tolist()):
+                if k == "max_courant":
+                    cmax = max(cmax, v)
+                else:
+                    sums[k] = sums[k] + v if k in sums else v
+        out = self._allreduce(sums)
+        out.update(self._allreduce({"max_courant": cmax}, op="max"))
+        return {k: out[k] for k in INVARIANTS}
 
     def diagnostics(self) -> Dict[str, float]:
         tot: Dict[str, float] = {}
@@ -563,12 +626,14 @@ class Solver:
         if "history" in iv:
             n_out = nsteps // io.history_interval + 1
             hpath = os.path.join(out, "history.zarr")
+            # io.history_fields: a selection among the prognostic and the derived fields
+            hfields = self.fields if io.history_fields is None else list(io.history_fields)
             if self.rank == 0:
                 os.makedirs(out, exist_ok=True)
-                HistoryWriter(hpath, self.fields, self.layout.N, self.layout.n, n_out,
+                HistoryWriter(hpath, hfields, self.layout.N, self.layout.n, n_out,
                               attrs={"config": self.config}, frame_chunks=self.mode != "spmd")
             self._barrier()
-            hist = HistoryWriter(hpath, self.fields, self.layout.N, self.layout.n, n_out, create=False)
+            hist = HistoryWriter(hpath, hfields, self.layout.N, self.layout.n, n_out, create=False)
         metrics = MetricsLogger(os.path.join(out, "metrics.jsonl") if "metrics" in iv else None,
                                 enabled=self.rank == 0)
         cells = 6 * self.layout.N ** 2
@@ -610,7 +675,7 @@ class Solver:
                 for k in lens[:8]:
                     self.runner.prepare(k)      # chunks shorter than a period: their remainder launch
             if deferred and ("watchdog" in iv or "metrics" in iv):
-                self._warm_checks()
+                self._warm_checks(derived="metrics" in iv)
             self._sync()
         wall0 = time.perf_counter()
         recoveries = 0
@@ -709,8 +774,14 @@ class Solver:
         (``pending``), i.e. while the next chunk steps."""
         t, sc = self.time, self.step_count
         snaps = []
-        for e in self.engines:
+        sel = self.cfg.io.history_fields
+        # selected fields: the derived ones are computed here, on the stepping stream
+        der = self._derived_all() if sel is not None and any(f in DERIVED_FIELDS for f in sel) else None
+        for j, e in enumerate(self.engines):
             v = e.tiles_view().detach()
+            if sel is not None:
+                v = torch.stack([der[j][0][DERIVED_FIELDS.index(f)] if f in DERIVED_FIELDS
+                                 else v[self.fields.index(f)] for f in sel])
             if async_copy:
                 h = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
                 h.copy_(v, non_blocking=True)
@@ -737,14 +808,24 @@ class Solver:
         rec = dict(step=self.step_count, time_s=self.time, sim_days=self.time / DAY, dt=self.dt)
         wall = time.perf_counter() - wall0
         rec["cell_updates_per_s"] = cells * done / max(wall, 1e-12)
+        swe = self.physics.name == "swe"
         if not deferred:
-            metrics.log(**rec, **self.diagnostics())
+            extra = {}
+            if swe:
+                inv = self.invariants()
+                extra = {k: inv[k] for k in METRIC_INVARIANTS}
+            metrics.log(**rec, **self.diagnostics(), **extra)
             return
         keys, vals = [], []
         for e in self.engines:
             for k, v in e.physics.diagnostics(e.tiles_view(), e.tens).items():
                 keys.append(k)
                 vals.append(v.reshape(()).to(torch.float64))
+        if swe:      # the one-launch reduction (ops/derived.py), through the same pinned copy
+            for _, inv in self._derived_all():
+                for k in METRIC_INVARIANTS:
+                    keys.append(k)
+                    vals.append(inv[INVARIANTS.index(k)])
         dev = torch.stack(vals)
         h = torch.empty(dev.shape, dtype=dev.dtype, pin_memory=True)
         h.copy_(dev, non_blocking=True)
@@ -754,11 +835,11 @@ class Solver:
         def work():
             tot: Dict[str, float] = {}
             for k, v in zip(keys, h.tolist()):
-                tot[k] = tot.get(k, 0.0) + v
+                tot[k] = max(tot[k], v) if k == "max_courant" and k in tot else tot.get(k, 0.0) + v
             metrics.log(**rec, **tot)
         pending.append((ev, work))
 
-    def _warm_checks(self) -> None:
+    def _warm_checks(self, derived: bool = False) -> None:
         """Run the watchdog and metrics reductions once before the clock
         starts.  Their first use in a process loads the kernels' code objects
         and the first pinned host blocks: measured on a 2-day C48 run
@@ -771,6 +852,8 @@ class Solver:
         hf.copy_(flag, non_blocking=True)
         hv = torch.empty((len(vals),), dtype=torch.float64, pin_memory=True)
         hv.copy_(torch.stack(vals), non_blocking=True)
+        if derived and self.physics.name == "swe":      # the derived-field kernels of the metrics records
+            self._derived_all()
         torch.cuda.current_stream().synchronize()
 
     def _watchdog(self, pending: List[Any], deferred: bool) -> bool:

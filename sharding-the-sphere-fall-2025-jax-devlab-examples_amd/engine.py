@@ -195,6 +195,33 @@ class Engine:
         d = self.physics.diagnostics(self.tiles_view(), self.tens)
         return {k: float(v) for k, v in d.items()}
 
+    @property
+    def derived_fields(self):
+        """``ops.derived.DerivedFields`` of this engine, built on first use
+        (its tables stay off ``tens``: the stepping paths do not see them)."""
+        if getattr(self, "_derived", None) is None:
+            from .ops.derived import DerivedFields
+            self._derived = DerivedFields(self)
+        return self._derived
+
+    def derived(self, exchange: bool = True):
+        """(fields [3, T, n, n] = vorticity, divergence, potential vorticity;
+        inv [8] float64, ``models.derived.INVARIANTS`` order) of the current
+        state, as device tensors.  A rank with remote ghosts exchanges first;
+        ``exchange=False`` when the caller ran ``derived_fields.start()`` /
+        ``finish()`` itself (several engines in one process)."""
+        d = self.derived_fields
+        if exchange:
+            d.start()
+            d.finish()
+        return d.compute()
+
+    def invariants(self, exchange: bool = True) -> Dict[str, float]:
+        """This rank's part of the invariants (sums; ``max_courant``: maximum)."""
+        from .models.derived import INVARIANTS
+        inv = self.derived(exchange)[1]
+        return dict(zip(INVARIANTS, inv.tolist()))
+
     def global_field(self, f: int = 0) -> np.ndarray:
         """Single-rank only: [6, N, N] float64 of field f."""
         assert self.layout.num_ranks == 1

@@ -159,6 +159,14 @@ class ShallowWater(Physics):
         speed = np.linalg.norm(wind, axis=-1) + np.sqrt(self.g * np.maximum(h, 0))
         return cfl * grid.min_spacing() / (2.0 * float(speed.max()))
 
+    def derived(self, q, recv, gmap, cmap, tens, tabs, order, T, n, ng, dt):
+        """Relative vorticity, divergence, potential vorticity [3, T, n, n] and
+        the invariants [8] of the padded state q [4, S] (models/derived.py:
+        the PyTorch twin of ops/csrc/derived_kernel.hip).  ``tabs`` / ``order``:
+        ``derived.derived_tables`` / ``derived.face_order`` of the rank."""
+        from .derived import derived_twin
+        return derived_twin(q, recv, gmap, cmap, tens, tabs, order, T, n, ng, self.g, 2.0 * self.omega, dt)
+
     def diagnostics(self, qi, tens):
         A = tens["area"]
         h = qi[0]

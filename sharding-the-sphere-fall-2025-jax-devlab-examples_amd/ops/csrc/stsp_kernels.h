@@ -181,6 +181,38 @@ int stsp_fused_tagh(void);
 int stsp_fused_record_words(int dtype);
 int stsp_fused_prime_launch(int dtype, const void* q, int S, const int* src, const int* code, int nent,
                             void* const* peer_ring, int ring, int epoch, hipStream_t stream);
+// Derived shallow-water fields and invariants of a state (derived_kernel.hip,
+// ops/derived.py; definitions in models/derived.py): two ordinary launches, one
+// workgroup per 16 x 16 cell block, then a one-workgroup fold of the block records.
+typedef struct DerivedDesc {
+  const void* Q;        // [4][S] state (h, M), padded layout; only interior cells are read directly
+  const void* recv;     // [R][4] remote ghost slots (nullable when R == 0)
+  const int* gmap;      // [T][4][mg][n] ghost map (layer 0 is read)
+  const int* cgmap;     // [T][4][mg][mg] RankPlan.corner_map (entry a = b = 0 is read)
+  const int* pedge;     // [T] tile sides on a panel edge (bits W, E, S, N)
+  const int* pe_base;   // [T][4][3][n] panel-edge interpolation pairs (layer 0 is read)
+  const void* pe_t;     // [T][4][3][n]
+  const void* cdx;      // [T][3][n][n+1] x-edge chords, south to north (m)
+  const void* cdy;      // [T][3][n+1][n] y-edge chords, west to east (m)
+  const void* mx;       // [T][3][n+1] x-edge unit normals
+  const void* my;       // [T][3][n+1]
+  const void* ex;       // [T][n][n+1] x-edge lengths
+  const void* ey;       // [T][n+1][n]
+  const void* invA;     // [T][n][n]
+  const void* area;     // [T][n][n]
+  const void* idxy;     // [T][n][n] 1/dx + 1/dy
+  const void* b;        // [T][n][n] topography
+  const void* rz;       // [T][n][n] z of the unit cell centre
+  void* fields;         // [3][T][n][n] out: zeta, delta, q
+  double* partials;     // [nblocks][8] block records (5 sums, 1 max, 2 spare)
+  double* inv;          // [8] out: mass, energy, potential enstrophy, circulation, |circulation|, max Courant
+  int ntile, n, S, mg, pw;  // as StageDesc
+  int nrecv;            // rows of recv
+  int nblocks;          // ntile * ceil(n / 16)^2
+  double g, omega2, dt;
+} DerivedDesc;
+int stsp_derived_launch(int dtype, const DerivedDesc* d, hipStream_t stream);
+int stsp_derived_desc_size(void);
 // Direct xGMI halo build constants: protocol (0 counters, 1 tagged granules), ring slots.
 int stsp_xg_protocol(void);
 int stsp_xg_slots(void);

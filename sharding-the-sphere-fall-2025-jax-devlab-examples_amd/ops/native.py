@@ -81,6 +81,21 @@ class March3Desc(ctypes.Structure):
     ]
 
 
+class DerivedDesc(ctypes.Structure):
+    """Mirror of DerivedDesc (stsp_kernels.h): derived fields and invariants."""
+    _fields_ = [
+        ("Q", ctypes.c_void_p), ("recv", ctypes.c_void_p), ("gmap", ctypes.c_void_p), ("cgmap", ctypes.c_void_p),
+        ("pedge", ctypes.c_void_p), ("pe_base", ctypes.c_void_p), ("pe_t", ctypes.c_void_p),
+        ("cdx", ctypes.c_void_p), ("cdy", ctypes.c_void_p), ("mx", ctypes.c_void_p), ("my", ctypes.c_void_p),
+        ("ex", ctypes.c_void_p), ("ey", ctypes.c_void_p), ("invA", ctypes.c_void_p), ("area", ctypes.c_void_p),
+        ("idxy", ctypes.c_void_p), ("b", ctypes.c_void_p), ("rz", ctypes.c_void_p),
+        ("fields", ctypes.c_void_p), ("partials", ctypes.c_void_p), ("inv", ctypes.c_void_p),
+        ("ntile", ctypes.c_int), ("n", ctypes.c_int), ("S", ctypes.c_int), ("mg", ctypes.c_int), ("pw", ctypes.c_int),
+        ("nrecv", ctypes.c_int), ("nblocks", ctypes.c_int),
+        ("g", ctypes.c_double), ("omega2", ctypes.c_double), ("dt", ctypes.c_double),
+    ]
+
+
 def lib_path() -> str:
     return _build.lib_for(os.environ.get("STSP_VARIANT", ""))
 
@@ -121,6 +136,13 @@ def load(build_if_missing: bool = True):
         L.stsp_fused_record_words.restype = ci
         L.stsp_fused_prime_launch.argtypes = [ci, vp, ci, vp, vp, ci, vp, ci, ci, vp]
         L.stsp_fused_prime_launch.restype = ci
+        L.stsp_derived_launch.argtypes = [ci, ctypes.POINTER(DerivedDesc), vp]
+        L.stsp_derived_launch.restype = ci
+        L.stsp_derived_desc_size.argtypes = []
+        L.stsp_derived_desc_size.restype = ci
+        if L.stsp_derived_desc_size() != ctypes.sizeof(DerivedDesc):
+            raise RuntimeError(f"DerivedDesc: ctypes mirror is {ctypes.sizeof(DerivedDesc)} bytes, "
+                               f"the library's {L.stsp_derived_desc_size()} (stale libstsp.so?)")
         _declare_runtime(L)
         _declare_tt(L)
         L.stsp_schedule_spin.argtypes = [ci]
