@@ -19,23 +19,21 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libstsp.so")
 SOURCES = ["stage_kernel.hip", "march_kernel.hip", "march3_kernel.hip", "fused_step.hip", "derived_kernel.hip", "tt_kernels.hip", "tt_persist.hip", "runtime.cpp"]
-HEADERS = ["stsp_kernels.h", "stage_common.h", "march_common.h", "tt_common.h", "runtime.h", "rccl_abi.h"]
+HEADERS = ["stsp_kernels.h", "stage_common.h", "xg_ring.h", "xg_codec.h", "march_common.h", "tt_common.h", "runtime.h", "rccl_abi.h"]
 ARCH = os.environ.get("STSP_OFFLOAD_ARCH", "gfx950")
 # library variants: "" = production; "diag" = in-kernel phase stamps of the
-# stage kernel (-DSTSP_STAMPS); "xgc" = the arrival-counter hand-off of the
-# xGMI halo instead of tagged granules (STSP_XG_TAG=0); the others are A/B
+# stage kernel (-DSTSP_STAMPS); the others are A/B
 # switches of kept alternatives (unfused faces, block-wide panel-edge fix-up,
 # own-cell wave placement, nine waves, library sqrt, compare+select slopes,
 # march waves per SIMD) and the timing-only fused-step probe fp_alledge;
 # xgfence: system-scope fences around the fused step's xGMI ring (multi-rank
-# visibility diagnostic); xgaos: the record-major ring layout of round 5
-# (STSP_XG_SOA=0), the A/B of profiles/r6_ring
-VARIANT_FLAGS = {"": [], "diag": ["-DSTSP_STAMPS"], "xgc": ["-DSTSP_XG_TAG=0"],
+# visibility diagnostic)
+VARIANT_FLAGS = {"": [], "diag": ["-DSTSP_STAMPS"],
                  "unfused": ["-DSTSP_FUSE_FACES=0"], "pe0": ["-DSTSP_PE_WAVE=0"],
                  "ownw0": ["-DSTSP_OWN_SKIP0=0"], "w9": ["-DSTSP_W10=0"], "swsqrt": ["-DSTSP_HW_SQRT=0"],
                  "selslope": ["-DSTSP_SIGN_SLOPE=0"], "wpe6": ["-DSTSP_WPE=6"], "wpe7": ["-DSTSP_WPE=7"],
                  "fp_alledge": ["-DSTSP_FPROBE_ALLEDGE=1"],
-                 "xgfence": ["-DSTSP_XG_FENCE=1"], "xgaos": ["-DSTSP_XG_SOA=0"]}
+                 "xgfence": ["-DSTSP_XG_FENCE=1"]}
 
 
 def lib_for(variant: str = "") -> str:

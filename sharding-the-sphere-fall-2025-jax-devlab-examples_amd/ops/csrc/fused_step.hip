@@ -278,53 +278,6 @@ __device__ __forceinline__ void to_global(int fr, T xi, T xj, T xn, T& o0, T& o1
   o2 = ai == 2 ? xi : (aj == 2 ? xj : xn);
 }
 
-// A cell of the tagged in-launch hand-off (FArgs::hx): its 4 field values in
-// HX<T>::W 64-bit granules, each {tag, payload} and single-copy atomic.  fp64:
-// 5 granules of a 12-bit tag and 52 payload bits (the 256 value bits in 5 x 52
-// = 260), against 8 granules of a 32-bit tag and 32 payload bits; fp32: 4
-// granules of a 32-bit tag and one value.  12 tag bits suffice: a slot holds
-// this step's value (tag want) or the value two steps older (want - 2 mod
-// 4096), never anything else (profiles/r6_handoff).
-template <typename T> struct HX;
-template <> struct HX<double> {
-  static constexpr int W = 5;
-  static constexpr unsigned long long M52 = (1ull << 52) - 1;
-  __device__ static void pack(const double (&q)[4], unsigned tag, unsigned long long (&g)[5]) {
-    const unsigned long long u0 = __builtin_bit_cast(unsigned long long, q[0]);
-    const unsigned long long u1 = __builtin_bit_cast(unsigned long long, q[1]);
-    const unsigned long long u2 = __builtin_bit_cast(unsigned long long, q[2]);
-    const unsigned long long u3 = __builtin_bit_cast(unsigned long long, q[3]);
-    const unsigned long long t = (unsigned long long)(tag & 0xFFFu) << 52;
-    g[0] = t | (u0 & M52);
-    g[1] = t | (u0 >> 52) | ((u1 << 12) & M52);
-    g[2] = t | (u1 >> 40) | ((u2 << 24) & M52);
-    g[3] = t | (u2 >> 28) | ((u3 << 36) & M52);
-    g[4] = t | (u3 >> 16);
-  }
-  __device__ static bool tag_ok(unsigned long long g, unsigned want) { return (unsigned)(g >> 52) == (want & 0xFFFu); }
-  __device__ static unsigned tag_of(unsigned long long g) { return (unsigned)(g >> 52); }
-  __device__ static void unpack(const unsigned long long (&g)[5], double (&q)[4]) {
-    const unsigned long long c0 = g[0] & M52, c1 = g[1] & M52, c2 = g[2] & M52, c3 = g[3] & M52, c4 = g[4] & M52;
-    q[0] = __builtin_bit_cast(double, c0 | (c1 << 52));
-    q[1] = __builtin_bit_cast(double, (c1 >> 12) | (c2 << 40));
-    q[2] = __builtin_bit_cast(double, (c2 >> 24) | (c3 << 28));
-    q[3] = __builtin_bit_cast(double, (c3 >> 36) | (c4 << 16));
-  }
-};
-template <> struct HX<float> {
-  static constexpr int W = 4;
-  __device__ static void pack(const float (&q)[4], unsigned tag, unsigned long long (&g)[4]) {
-#pragma unroll
-    for (int f = 0; f < 4; ++f) g[f] = ((unsigned long long)tag << 32) | __builtin_bit_cast(unsigned, q[f]);
-  }
-  __device__ static bool tag_ok(unsigned long long g, unsigned want) { return (unsigned)(g >> 32) == want; }
-  __device__ static unsigned tag_of(unsigned long long g) { return (unsigned)(g >> 32); }
-  __device__ static void unpack(const unsigned long long (&g)[4], float (&q)[4]) {
-#pragma unroll
-    for (int f = 0; f < 4; ++f) q[f] = __builtin_bit_cast(float, (unsigned)g[f]);
-  }
-};
-
 // swap a value between the lanes of a pair (2 j, 2 j + 1): DPP quad_perm
 // [1, 0, 3, 2], one v_mov_dpp per 32 bits, every lane of the wave active
 template <typename T>
@@ -530,33 +483,13 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
   auto load_state_of = [&](int src, T (&Q)[4], const T* Qin, int xe_) {
     const bool loaded = src >= 0 || (XG && src <= -2);
     if (XG && src <= -2) {
-      // another rank's cell: spin on its packed granules (HX<T>) in ring slot
-      // xe % SLOTS until every tag carries this step (xe + 1; a slot holds this
-      // step's record or the one SLOTS steps older); a timeout sets err and
-      // falls through
-      constexpr int HW = HX<T>::W;
-      const gu64* rp = (const gu64*)(a.recv) + (long)(xe_ % STSP_XG_SLOTS) * a.ring;
-      const int nrec = a.ring / HW, rec = -2 - src;
-      const unsigned want = (unsigned)xe_ + 1u;
-      unsigned long long gr[HW];
-      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-      for (;;) {
-        bool ok = true;
-        if (STSP_XG_FENCE) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-#pragma unroll
-        for (int k = 0; k < HW; ++k)
-          gr[k] = __hip_atomic_load(rp + ring_word(nrec, HW, rec, k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        const unsigned er = __hip_atomic_load((gu32*)a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int k = 0; k < HW; ++k) ok &= HX<T>::tag_ok(gr[k], want);
-        if (ok) break;
-        if (er != 0) break;
-        if ((long long)(__builtin_amdgcn_s_memrealtime() - t0) > a.timeout_ticks) {
-          fused_fail(a.err, 1u, bid, xe_, -2 - src, (int)HX<T>::tag_of(gr[0]));
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
+      // another rank's cell: spin on its packed granules (HX<T>) in the ring
+      // until every tag carries this step; a timeout sets err and falls through
+      unsigned long long gr[HX<T>::W];
+      const XgRec r = ring_slot_record<HX<T>>(a.recv, a.ring, xg_in_slot(xe_), -2 - src);
+      xg_wait<HX<T>, XG_RING_SCOPE, STSP_XG_FENCE != 0>(r, xg_in_tag(xe_), a.err, a.timeout_ticks, gr, [&] {
+        fused_fail(a.err, 1u, bid, xe_, -2 - src, (int)HX<T>::tag_of(gr[0]));
+      });
       HX<T>::unpack(gr, Q);
     } else if (loaded) {
       const unsigned S = (unsigned)a.S;
@@ -569,28 +502,18 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
       for (int f = 0; f < 4; ++f) Q[f] = T(0);
     }
   };
+  // cell `so` of slot `slot` of the tagged hand-off buffer (FArgs::hx)
+  auto hx_record = [&](unsigned so, int slot) -> XgRec {
+    const unsigned S = (unsigned)a.S;
+    return {(gu64*)a.hx + (size_t)slot * HX<T>::W * S + so, (long)S};
+  };
   // a window cell of another block at step xe_ > launch start, tagged hand-off
   auto load_tagged = [&](int src_, T (&q)[4], int xe_) {
-    constexpr int HW = HX<T>::W;
-    const unsigned S = (unsigned)a.S;
-    const gu64* hp = (const gu64*)a.hx + (size_t)(xe_ & 1) * HW * S + (unsigned)src_;
-    const unsigned want = (unsigned)xe_ + 1u;
-    unsigned long long gr[HW];
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    for (;;) {
-      bool ok = true;
-#pragma unroll
-      for (int k = 0; k < HW; ++k) gr[k] = __hip_atomic_load(hp + (size_t)k * S, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-      for (int k = 0; k < HW; ++k) ok &= HX<T>::tag_ok(gr[k], want);
-      if (ok) break;
-      if (__hip_atomic_load((gu32*)a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-      if ((long long)(__builtin_amdgcn_s_memrealtime() - t0) > a.timeout_ticks) {
-        fused_fail(a.err, 2u, bid, xe_, src_, (int)HX<T>::tag_of(gr[0]));
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
+    unsigned long long gr[HX<T>::W];
+    const XgRec r = hx_record((unsigned)src_, xe_ & 1);
+    xg_wait<HX<T>, XG_LOCAL_SCOPE>(r, xg_in_tag(xe_), a.err, a.timeout_ticks, gr, [&] {
+      fused_fail(a.err, 2u, bid, xe_, src_, (int)HX<T>::tag_of(gr[0]));
+    });
     HX<T>::unpack(gr, q);
   };
   auto load_state = [&](const T* Qin, int xe_) { load_state_of(src, Q, Qin, xe_); };
@@ -853,25 +776,19 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
     // wait for the producers' previous step (wave 0 polls) ...
     const int p = tid < a.PM ? a.prod[(long)bid * a.PM + tid] : -1;
     const int pa = p >= 0 ? p : bid;
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    for (;;) {
-      // the producers' step counters and the error word in one round trip per
-      // poll (round 4 read them one after the other: no measurable difference
-      // at C96, profiles/r5_fused/poll_ab)
-      // (every lane loads: lanes without a producer read the block's own
-      // counter, so no branch splits the two loads)
-      const unsigned er = __hip_atomic_load((gu32*)a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // (the error word is read after a failed poll, xg_spin; reading it with
+    // the counters in one round trip made no measurable difference at C96,
+    // profiles/r5_fused/poll_ab)
+    // (every lane loads: lanes without a producer read the block's own counter)
+    bool ok = false;
+    xg_spin(a.err, a.timeout_ticks, [&] {
       const int e = __hip_atomic_load(a.epoch + pa, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const bool ok = p < 0 || e >= xe;
-      if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
-      if (er != 0) break;
-      if ((long long)(__builtin_amdgcn_s_memrealtime() - t0) > a.timeout_ticks) {
-        if (!ok) fused_fail(a.err, 2u, bid, xe, p, __hip_atomic_load(a.epoch + p, __ATOMIC_RELAXED,
-                                                                      __HIP_MEMORY_SCOPE_AGENT));
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
+      ok = p < 0 || e >= xe;
+      return __builtin_amdgcn_ballot_w64(!ok) == 0;
+    }, [&] {
+      if (!ok) fused_fail(a.err, 2u, bid, xe, p, __hip_atomic_load(a.epoch + p, __ATOMIC_RELAXED,
+                                                                    __HIP_MEMORY_SCOPE_AGENT));
+    });
   } else {
     // ... while the other waves compute the inner stage-1 faces (tagged
     // hand-off: every wave; the ring loads below are the wait)
@@ -903,17 +820,11 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
           const int k = a.pidx[(long)bid * W * W + cv * W + cu];
           if (k < 0) return;
           const int p = a.prod[(long)bid * a.PM + k];
-          const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-          for (;;) {
-            const int e = __hip_atomic_load(a.epoch + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (e >= xe) break;
-            if (__hip_atomic_load((gu32*)a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-            if ((long long)(__builtin_amdgcn_s_memrealtime() - t0) > a.timeout_ticks) {
-              fused_fail(a.err, 2u, bid, xe, p, e);
-              break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-          }
+          int e = 0;
+          xg_spin(a.err, a.timeout_ticks, [&] {
+            e = __hip_atomic_load(a.epoch + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return e >= xe;
+          }, [&] { fused_fail(a.err, 2u, bid, xe, p, e); });
         };
         if (tid >= B * B && owner) poll_prod(u, v);
 #pragma unroll
@@ -1103,13 +1014,9 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
     unsigned so = (unsigned)src;
     asm volatile("" : "+v"(so));
     if (tagh && !last) {     // tagged granules for the next step's readers (word-major)
-      constexpr int HW = HX<T>::W;
-      gu64* hp = (gu64*)a.hx + (size_t)((xe + 1) & 1) * HW * S + so;
-      unsigned long long g[HW];
-      HX<T>::pack(Q, (unsigned)xe + 2u, g);
-#pragma unroll
-      for (int k = 0; k < HW; ++k)
-        __hip_atomic_store(hp + (size_t)k * S, g[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      unsigned long long g[HX<T>::W];
+      HX<T>::pack(Q, xg_out_tag(xe), g);
+      xg_store<HX<T>, XG_LOCAL_SCOPE>(hx_record(so, (xe + 1) & 1), g);
     } else if (MULTI) {      // write-through: the next step's readers may sit on another XCD
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
@@ -1147,19 +1054,14 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
         }
       }
     }
-    if constexpr (XG) {   // cells other ranks read: straight into their rings, packed, tag xe + 2
-      constexpr int HW = HX<T>::W;
+    if constexpr (XG) {   // cells other ranks read: straight into their rings, packed
       const int* xp = a.xpush + ((long)bid * B * B + (v - R) * B + (u - R)) * a.K;
-      unsigned long long g[HW];
-      HX<T>::pack(Q, (unsigned)xe + 2u, g);
+      unsigned long long g[HX<T>::W];
+      HX<T>::pack(Q, xg_out_tag(xe), g);
       for (int k = 0; k < a.K; ++k) {
         const int code = xp[k];
         if (code < 0) break;
-        gu64* dst = ((gu64*)(a.peer_ring[code >> 24])) + (long)((xe + 1) % STSP_XG_SLOTS) * a.ring;
-        const int nrec = a.ring / HW, rec = code & 0xFFFFFF;
-#pragma unroll
-        for (int w = 0; w < HW; ++w)
-          __hip_atomic_store(dst + ring_word(nrec, HW, rec, w), g[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        xg_store<HX<T>, XG_RING_SCOPE>(ring_record<HX<T>>(a.peer_ring, a.ring, code, xg_out_slot(xe)), g);
       }
     }
   }
@@ -1222,7 +1124,7 @@ int launch_fused(const FusedDesc* d, hipStream_t s) {
   if (!a.sched || !a.nrmf) return -4;
   if (a.nsteps > 1 && (!a.prod || a.PM <= 0 || a.PM > 64 || !d->epoch || !d->err)) return -7;
   a.mdiv_n = magic_div((unsigned)d->n, (unsigned long long)d->N + 1);
-  if (d->xg && (!STSP_XG_TAG || !d->recv || !d->peer_ring || !d->xpush || !d->epoch || !d->err || d->ring <= 0 ||
+  if (d->xg && (!d->recv || !d->peer_ring || !d->xpush || !d->epoch || !d->err || d->ring <= 0 ||
                 d->K <= 0))
     return -6;
   const dim3 grid(d->nblocks), block(D::NT);
@@ -1314,26 +1216,15 @@ extern "C" int stsp_fused_launch(int dtype, const FusedDesc* d, hipStream_t stre
 // Compile-time sizes of the fused kernel (host checks): ghost entries and corner faces per block.
 // Initial delivery into the fused step's xGMI rings, packed records (HX<T>):
 // entry i stores cell src[i] of the state (F = 4 fields, stride S) into ring
-// slot epoch % SLOTS of rank code[i] >> 24, record code[i] & 0xFFFFFF, tag
-// epoch + 1.  ring: granules per slot.
+// slot and record code[i] names, as an input record of step `epoch`
+// (xg_ring.h).  ring: granules per slot.
 template <typename T>
 __global__ __launch_bounds__(256) void fused_prime_kernel(const T* __restrict__ q, int S,
                                                           const int* __restrict__ src, const int* __restrict__ code,
                                                           int nent, T* const* peer_ring, int ring, int epoch) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < nent) {
-    constexpr int HW = HX<T>::W;
-    const int c = code[i];
-    T v[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) v[f] = q[(long)f * S + src[i]];
-    unsigned long long g[HW];
-    HX<T>::pack(v, (unsigned)epoch + 1u, g);
-    gu64* dst = ((gu64*)(peer_ring[c >> 24])) + (long)(epoch % STSP_XG_SLOTS) * ring;
-    const int nrec = ring / HW;
-#pragma unroll
-    for (int w = 0; w < HW; ++w)
-      __hip_atomic_store(dst + ring_word(nrec, HW, c & 0xFFFFFF, w), g[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    xg_prime_record<HX<T>, 4>(q, S, src[i], code[i], peer_ring, ring, epoch);
   }
   __threadfence_system();
 }

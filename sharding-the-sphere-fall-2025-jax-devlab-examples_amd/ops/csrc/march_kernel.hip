@@ -119,34 +119,13 @@ void march_kernel(Args<T> a, int ncs, int nrs, int njobs) {
           if (ca < mg && cb < mg) m = a.cgmap[((tile * 4 + (cx >= n ? 1 : 0) + (y >= n ? 2 : 0)) * mg + ca) * mg + cb];
         }
         if (m < 0) {                               // remote slot -1 - m: spin on its granules
-          constexpr int G = sizeof(T) / 4;
-          const gu64* rp = ((const gu64*)(a.recv)) + (long)(xe % STSP_XG_SLOTS) * a.ring;
-          const int nrec = a.ring / (4 * G), rec = -1 - m;
-          const unsigned want = (unsigned)xe + 1u;
-          unsigned long long gr[4 * G];
-          const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-          for (;;) {
-            bool ok = true;
-#pragma unroll
-            for (int k = 0; k < 4 * G; ++k) {
-              gr[k] = __hip_atomic_load(rp + ring_word(nrec, 4 * G, rec, k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-              ok &= (unsigned)(gr[k] >> 32) == want;
-            }
-            if (ok) break;
-            if (__hip_atomic_load((gu32*)a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-            if ((long long)(__builtin_amdgcn_s_memrealtime() - t0) > a.timeout_ticks) {
-              __hip_atomic_store((gu32*)a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-          }
-#pragma unroll
-          for (int f = 0; f < 4; ++f) {
-            if constexpr (G == 2)
-              q[f] = __builtin_bit_cast(T, (gr[2 * f + 1] << 32) | (gr[2 * f] & 0xFFFFFFFFull));
-            else
-              q[f] = __builtin_bit_cast(T, (unsigned)gr[f]);
-          }
+          using C = XgPlain<T, 4>;
+          unsigned long long gr[C::W];
+          const XgRec r = ring_slot_record<C>(a.recv, a.ring, xg_in_slot(xe), -1 - m);
+          xg_wait<C, XG_RING_SCOPE>(r, xg_in_tag(xe), a.err, a.timeout_ticks, gr, [&] {
+            __hip_atomic_store((gu32*)a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          });
+          C::unpack(gr, q);
           return;
         }
       }
@@ -480,25 +459,11 @@ void march_kernel(Args<T> a, int ncs, int nrs, int njobs) {
 #pragma unroll
           for (int f = 0; f < 4; ++f) bst<0>(o[f], rO, (unsigned)pt[k] * ES, f * fs);
         } else if (XG && pt[k] <= -2) {
-          // another rank's ghost: its ring slot (xe + 1) % SLOTS, tag xe + 2
-          constexpr int G = sizeof(T) / 4;
-          const int code = -2 - pt[k];
-          gu64* dst = ((gu64*)(a.peer_ring[code >> 24])) + (long)((xe + 1) % STSP_XG_SLOTS) * a.ring;
-          const int nrec = a.ring / (4 * G), rec = code & 0xFFFFFF;
-          const unsigned long long tag = (unsigned long long)((unsigned)xe + 2u) << 32;
-#pragma unroll
-          for (int f = 0; f < 4; ++f) {
-            if constexpr (G == 2) {
-              const unsigned long long bits = __builtin_bit_cast(unsigned long long, o[f]);
-              __hip_atomic_store(dst + ring_word(nrec, 8, rec, 2 * f), tag | (bits & 0xFFFFFFFFull), __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_SYSTEM);
-              __hip_atomic_store(dst + ring_word(nrec, 8, rec, 2 * f + 1), tag | (bits >> 32), __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_SYSTEM);
-            } else {
-              __hip_atomic_store(dst + ring_word(nrec, 4, rec, f), tag | __builtin_bit_cast(unsigned, o[f]),
-                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-          }
+          // another rank's ghost: into its ring, as an input record of the next stage
+          using C = XgPlain<T, 4>;
+          unsigned long long g[C::W];
+          C::pack(o, xg_out_tag(xe), g);
+          xg_store<C, XG_RING_SCOPE>(ring_record<C>(a.peer_ring, a.ring, -2 - pt[k], xg_out_slot(xe)), g);
         }
       }
     }
@@ -581,7 +546,7 @@ __global__ void dpp_probe_kernel(const double* in, double* out, float* outf) {
 // block list.
 extern "C" int stsp_march_launch(int dtype, int rows, const StageDesc* d, hipStream_t stream) {
   if (d->remote || d->blocks) return -13;
-  if (d->xg && (!STSP_XG_TAG || !d->recv || !d->peer_ring || !d->epoch || !d->err || !d->gmap || d->ring <= 0))
+  if (d->xg && (!d->recv || !d->peer_ring || !d->epoch || !d->err || !d->gmap || d->ring <= 0))
     return -13;
   if (d->pw != d->n + 2 * d->mg || d->mg < 2 || d->n < 2) return -5;
   if (!d->pedge || !d->pe_base || !d->pe_t || !d->push || !d->mx || !d->my) return -12;

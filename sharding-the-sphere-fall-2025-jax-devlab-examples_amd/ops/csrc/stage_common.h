@@ -1,53 +1,13 @@
-// Device helpers shared by the fused stage kernel (stage_kernel.hip) and the
-// persistent step kernel (step_kernel.hip): physics constants, the block
-// role geometry, branch-free math, buffer access, the SWE Rusanov flux and
-// the launch-argument record.  Everything lives in an anonymous namespace:
-// each translation unit gets its own copy of these inline templates.
+// Device helpers shared by the stage kernel (stage_kernel.hip), the streaming
+// stages (march_kernel.hip, march3_kernel.hip) and the fused step
+// (fused_step.hip): physics constants, the block role geometry, branch-free
+// math, buffer access, the SWE Rusanov flux and the launch-argument record.
+// Everything lives in an anonymous namespace: each translation unit gets its
+// own copy of these inline templates.  The halo hand-off protocol is xg_ring.h.
 #pragma once
 #include "stsp_kernels.h"
+#include "xg_ring.h"
 
-// Publish protocol of the arrival-counter hand-off (STSP_XG_TAG=0 below):
-// every storing wave drains, then a release add per peer (one L2 write-back
-// per producing block).  Measured alternatives (profiles/r1_xg_fence_probe.jsonl,
-// loopback C96 us/step, plain step 17.1): a __threadfence_system() before the
-// add 117.5 (the fence is seq_cst: every wave also invalidates L2), the
-// release add 28.6, a relaxed add after the drain 26.8 (not a release in the
-// model); the probes are gone, the release add stays.
-// Halo hand-off form (stsp_kernels.h, xg fields):
-//   0 = arrival counters (drain + release add per producing block, block-level poll)
-//   1 = tagged granules: the data is the flag.  Each 32-bit word of a ghost cell
-//       travels as ONE 8-byte {tag = stage epoch + 1, payload} relaxed system-scope
-//       atomic store (single-copy atomic, so never torn); the consumer thread
-//       re-reads its cell's granules until every tag matches.  The producer
-//       neither drains nor signals, and the consumer skips the separate poll
-//       round trip (cdna_hip_programming.md Guideline 16, R2).
-//   Measured (tools/xg_tag_round.sh, profiles/r1_xg_tag_probe.jsonl, C96 fp64 µs/step):
-//   loopback 28.9 (counters) -> 24.9 (tags); two ranks sharing one GPU 26.9 -> 21.8.
-#ifndef STSP_XG_TAG
-#define STSP_XG_TAG 1
-#endif
-// Ring slots.  A rank reads slot e % S during its stage e while a peer writes
-// slot (e_p + 1) % S during its stage e_p.  A peer can have STARTED at most two
-// stages past us: its stage e + 2 needs its stage e + 1 complete, which waited
-// for our stage-e output, i.e. our stage e started and e - 1 completed.  So the
-// peer writes slot (e + 1 .. e + 3) % S, never e % S, iff S does not divide 1,
-// 2 or 3: S = 4 (three slots left a window where a peer two stages ahead
-// overwrote the slot a slow block of ours was still reading).
-#define STSP_XG_SLOTS 4
-// Ring record layout.  A slot holds nrec = ring / NW records of NW words (NW =
-// F G tagged 8-byte granules, or F values under STSP_XG_TAG=0).
-// STSP_XG_SOA=1 (default): word-major, word w of record r at w nrec + r.  The
-// host numbers a consumer's records by owner rank, then cell id (row order),
-// so the lanes of one store or poll instruction touch consecutive 8-byte words
-// (up to 512 contiguous bytes per wave) instead of words NW x 8 bytes apart
-// (record-major, r NW + w: STSP_XG_SOA=0, the round-5 layout, kept for the A/B
-// in profiles/r6_ring).
-#ifndef STSP_XG_SOA
-#define STSP_XG_SOA 1
-#endif
-__device__ __forceinline__ long ring_word(int nrec, int nw, int rec, int w) {
-  return STSP_XG_SOA ? (long)w * nrec + rec : (long)rec * nw + w;
-}
 // Own-cell waves: 1 = the first waves not on SIMD 0, 0 = waves 0 .. n-1.
 #ifndef STSP_OWN_SKIP0
 #define STSP_OWN_SKIP0 1
@@ -331,9 +291,10 @@ struct Args {
   // direct xGMI halo (XG kernels only, see stsp_kernels.h)
   int ring;
   T* const* peer_ring;
-  unsigned long long* const* peer_cnt;
-  const unsigned long long* cnt;
-  const unsigned long long* nprod;
+  // (three unused slots: with bmask and the fields below 24 bytes further up, the
+  // wide scalar loads of the kernel arguments group differently, which costs the XG
+  // stage kernels 2-4 SGPRs, SGPR spills and a wave per SIMD; profiles/xg_ring)
+  const void* kernarg_pad[3];
   const int* bmask;
   int* epoch;
   int* err;
@@ -392,9 +353,7 @@ __device__ __forceinline__ void swe_flux(const T (&wl)[4], const T (&wr)[4], con
 // agent-scope relaxed atomics, which gfx950 lowers to global_load/store ... sc1
 // (L1 bypass / write-through), the hand-off form of cdna_hip_programming.md
 // Guideline 16 (R1) measured valid for one workgroup per CU.
-typedef __attribute__((address_space(1))) unsigned long long gu64;
-typedef __attribute__((address_space(1))) unsigned int gu32;
-
+// (gu64 / gu32, the global address-space words of these atomics: xg_ring.h)
 template <bool SYNC, typename T>
 __device__ __forceinline__ T ld_state(const T* p) {
   if constexpr (!SYNC) {
@@ -404,24 +363,6 @@ __device__ __forceinline__ T ld_state(const T* p) {
   } else {
     return __builtin_bit_cast(T, __hip_atomic_load((gu32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
   }
-}
-
-// System-scope (cross-GPU) accesses of the direct xGMI halo: sc0 sc1, i.e.
-// no GPU cache keeps a copy, so a peer's store is seen by the next poll/load.
-template <typename T>
-__device__ __forceinline__ T ld_sys(const T* p) {
-  if constexpr (sizeof(T) == 8)
-    return __builtin_bit_cast(T, __hip_atomic_load((gu64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-  else
-    return __builtin_bit_cast(T, __hip_atomic_load((gu32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-}
-
-template <typename T>
-__device__ __forceinline__ void st_sys(T* p, T v) {
-  if constexpr (sizeof(T) == 8)
-    __hip_atomic_store((gu64*)p, __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  else
-    __hip_atomic_store((gu32*)p, __builtin_bit_cast(unsigned int, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // Stage output stores.  wt (block-uniform): write-through (agent-scope relaxed
@@ -487,9 +428,7 @@ Args<T> make_args(const StageDesc* d) {
   a.pew = 0;
   a.ring = d->ring;
   a.peer_ring = (T* const*)d->peer_ring;
-  a.peer_cnt = d->peer_cnt;
-  a.cnt = d->cnt;
-  a.nprod = d->nprod;
+  a.kernarg_pad[0] = a.kernarg_pad[1] = a.kernarg_pad[2] = nullptr;
   a.bmask = d->bmask;
   a.epoch = d->epoch;
   a.err = d->err;

@@ -35,10 +35,8 @@ namespace {
 // bypass, write-through); the launch-per-stage kernels use SYNC = false (the
 // persistent step kernel, step_kernel.hip, hands its halos off as granules).
 // XG = direct xGMI halo: a block reads its remote ghosts from this rank's
-// receive ring (slot epoch % STSP_XG_SLOTS) once they have arrived (tags match,
-// or the peers' arrival counters are complete), and every block stores the cells
-// its peers need into their rings (slot (epoch + 1) % STSP_XG_SLOTS).  Why four
-// slots and no reset: see STSP_XG_SLOTS; tags and counters only grow.
+// receive ring once their tags match, and every block stores the cells its
+// peers need into their rings (tagged granules, slots and tags: xg_ring.h).
 template <typename T, int P, int BX, int BY, int LIM, bool REMOTE, bool SYNC, bool XG = false>
 __device__ __forceinline__ void stage_body(const Args<T>& a, const int bid) {
   constexpr int F = Phys<P>::F;
@@ -123,11 +121,10 @@ __device__ __forceinline__ void stage_body(const Args<T>& a, const int bid) {
   // direct xGMI: the block's epoch and peer masks are issued before every other
   // load, so waiting for them (vmcnt counts in issue order) never waits for the
   // prefetch below and the poll can start one round trip into the kernel
-  int xe = 0, need = 0, feed = 0;
+  int xe = 0, need = 0;
   if constexpr (XG) {
     xe = a.epoch[bid];
     need = a.bmask[2 * bid];
-    feed = a.bmask[2 * bid + 1];
   }
   // panel-edge bits of the tile: a vector load (the compiler cannot prove the
   // array unwritten, so no s_load), issued before the prefetch and first used
@@ -361,28 +358,9 @@ __device__ __forceinline__ void stage_body(const Args<T>& a, const int bid) {
   if constexpr (!LATE_TAB) load_tab();
   STAMP(1);
 
-  // ---- 0b. direct xGMI: wait for the peers whose ghosts this block reads ------
+  // direct xGMI: only the blocks that read remote ghosts look them up
   bool rblk = REMOTE;
-  const T* rring = a.recv;
-  if constexpr (XG) {
-    rblk = need != 0;
-    rring = a.recv + (long)(xe % STSP_XG_SLOTS) * a.ring;   // tags: a.ring counts 8-byte granules, see below
-    if (!STSP_XG_TAG && rblk) {
-      if (tid < 32 && ((need >> tid) & 1)) {
-        const unsigned long long want = (unsigned long long)xe * a.nprod[tid];
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (__hip_atomic_load((gu64*)(a.cnt + tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < want) {
-          if (__hip_atomic_load((gu32*)a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-          if ((long long)(__builtin_amdgcn_s_memrealtime() - t0) > a.timeout_ticks) {
-            __hip_atomic_store((gu32*)a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-        }
-      }
-      __syncthreads();
-    }
-  }
+  if constexpr (XG) rblk = need != 0;
 
   // ---- 1. window (block + NG halo) -> LDS --------------------------------------
   // Own-cell threads store the state they prefetched, the ring threads load one
@@ -413,43 +391,18 @@ __device__ __forceinline__ void stage_body(const Args<T>& a, const int bid) {
           const int m = wgm;   // < 0: remote slot -1 - m (0 outside the ghost strips)
           if (m < 0) {
             from_recv = true;
-            if constexpr (XG && STSP_XG_TAG) {
-              // spin on this cell's granules until all carry this stage's tag
-              constexpr int G = sizeof(T) / 4;
-              const gu64* rp = ((const gu64*)(a.recv)) + (long)(xe % STSP_XG_SLOTS) * a.ring;
-              const int nrec = a.ring / (F * G), rec = -1 - m;
-              const unsigned want = (unsigned)xe + 1u;
-              unsigned long long gr[F * G];
-              const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-              for (;;) {
-                bool ok = true;
-#pragma unroll
-                for (int k = 0; k < F * G; ++k) {
-                  gr[k] = __hip_atomic_load(rp + ring_word(nrec, F * G, rec, k), __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_SYSTEM);
-                  ok &= (unsigned)(gr[k] >> 32) == want;
-                }
-                if (ok) break;
-                if (__hip_atomic_load((gu32*)a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-                if ((long long)(__builtin_amdgcn_s_memrealtime() - t0) > a.timeout_ticks) {
-                  __hip_atomic_store((gu32*)a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                  break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-              }
-#pragma unroll
-              for (int f = 0; f < F; ++f) {
-                if constexpr (G == 2)
-                  v[f] = __builtin_bit_cast(T, (gr[2 * f + 1] << 32) | (gr[2 * f] & 0xFFFFFFFFull));
-                else
-                  v[f] = __builtin_bit_cast(T, (unsigned)gr[f]);
-              }
-            } else if constexpr (XG) {
-              const int nrec = a.ring / F;
-#pragma unroll
-              for (int f = 0; f < F; ++f) v[f] = ld_sys(rring + ring_word(nrec, F, -1 - m, f));
+            if constexpr (XG) {
+              // spin on this cell's granules until all carry this stage's tag;
+              // a timeout sets err and falls through
+              using C = XgPlain<T, F>;
+              unsigned long long gr[C::W];
+              const XgRec r = ring_slot_record<C>(a.recv, a.ring, xg_in_slot(xe), -1 - m);
+              xg_wait<C, XG_RING_SCOPE>(r, xg_in_tag(xe), a.err, a.timeout_ticks, gr, [&] {
+            __hip_atomic_store((gu32*)a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          });
+              C::unpack(gr, v);
             } else {
-              const T* rp = rring + (long)(-1 - m) * F;
+              const T* rp = a.recv + (long)(-1 - m) * F;
 #pragma unroll
               for (int f = 0; f < F; ++f) v[f] = ld_state<SYNC>(rp + f);
             }
@@ -832,45 +785,17 @@ __device__ __forceinline__ void stage_body(const Args<T>& a, const int bid) {
     }
     STAMP(10);
     if constexpr (XG) {   // remote ghosts: straight into the consumer's ring
+      using C = XgPlain<T, F>;
+      unsigned long long g[C::W];
+      C::pack(o, xg_out_tag(xe), g);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        if (pt[k] < -1) {
-          const int code = -2 - pt[k];
-          if constexpr (STSP_XG_TAG) {
-            constexpr int G = sizeof(T) / 4;
-            gu64* dst = ((gu64*)(a.peer_ring[code >> 24])) + (long)((xe + 1) % STSP_XG_SLOTS) * a.ring;
-            const int nrec = a.ring / (F * G), rec = code & 0xFFFFFF;
-            const unsigned long long tag = (unsigned long long)((unsigned)xe + 2u) << 32;
-#pragma unroll
-            for (int f = 0; f < F; ++f) {
-              if constexpr (G == 2) {
-                const unsigned long long b = __builtin_bit_cast(unsigned long long, o[f]);
-                __hip_atomic_store(dst + ring_word(nrec, F * G, rec, 2 * f), tag | (b & 0xFFFFFFFFull),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(dst + ring_word(nrec, F * G, rec, 2 * f + 1), tag | (b >> 32), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_SYSTEM);
-              } else {
-                __hip_atomic_store(dst + ring_word(nrec, F, rec, f), tag | __builtin_bit_cast(unsigned, o[f]),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-              }
-            }
-          } else {
-            T* dst = a.peer_ring[code >> 24] + (long)((xe + 1) % STSP_XG_SLOTS) * a.ring;
-            const int nrec = a.ring / F, rec = code & 0xFFFFFF;
-#pragma unroll
-            for (int f = 0; f < F; ++f) st_sys(dst + ring_word(nrec, F, rec, f), o[f]);
-          }
-        }
+        if (pt[k] < -1)
+          xg_store<C, XG_RING_SCOPE>(ring_record<C>(a.peer_ring, a.ring, -2 - pt[k], xg_out_slot(xe)), g);
       }
     }
   }
   if constexpr (XG) {
-    if (!STSP_XG_TAG && feed) {   // publish: every storing wave drains, then one lane per peer counts
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid < 32 && ((feed >> tid) & 1))
-        __hip_atomic_fetch_add((gu64*)a.peer_cnt[tid], 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
     if (tid == 0) a.epoch[bid] = xe + 1;
   }
   STAMP(6);
@@ -933,8 +858,7 @@ int launch_t(const StageDesc* d, hipStream_t s) {
   if (d->pw != d->n + 2 * d->mg || d->mg < Phys<P>::NG || (d->limiter == 4 && d->mg < 3)) return -5;
   if (P != 1 && (!d->pedge || !d->pe_base || !d->pe_t || d->n < 2)) return -12;   // panel-edge tables
   if (!d->push || (d->remote && (!d->gmap || !d->blocks))) return -6;
-  if (d->xg && (d->remote || d->blocks || !d->gmap || !d->recv || !d->peer_ring || !d->peer_cnt || !d->cnt ||
-                !d->nprod || !d->bmask || !d->epoch || !d->err || d->ring <= 0))
+  if (d->xg && (d->remote || d->blocks || !d->gmap || !d->recv || !d->peer_ring || !d->bmask || !d->epoch || !d->err || d->ring <= 0))
     return -10;
   if constexpr (P == 1) return launch_l<T, P, BX, BY, 0>(d, s);  // diffusion: no reconstruction
   switch (d->limiter) {
@@ -979,39 +903,16 @@ __global__ __launch_bounds__(256) void pack_kernel(const T* __restrict__ q, int 
   for (int f = 0; f < F; ++f) send[(long)k * F + f] = q[(long)f * S + src];
 }
 
-// ---- direct xGMI halo: initial ghost delivery (no counter bump) -------------
-// Writes the ghosts of stage `epoch`'s input: slot epoch % SLOTS, tag epoch + 1.
+// ---- direct xGMI halo: initial ghost delivery -------------------------------
+// Writes the ghosts of stage `epoch`'s input (its slot and tag, xg_ring.h).
 template <typename T>
 __global__ __launch_bounds__(256) void xg_prime_kernel(const T* __restrict__ q, int S, int F,
                                                        const int* __restrict__ src, const int* __restrict__ code,
                                                        int nent, T* const* peer_ring, int ring, int epoch) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int slot = epoch % STSP_XG_SLOTS;
   if (i < nent) {
-    const int c = code[i];
-    if constexpr (STSP_XG_TAG) {
-      constexpr int G = sizeof(T) / 4;
-      gu64* dst = ((gu64*)(peer_ring[c >> 24])) + (long)slot * ring;
-      const int nrec = ring / (F * G), rec = c & 0xFFFFFF;
-      const unsigned long long tag = (unsigned long long)((unsigned)epoch + 1u) << 32;
-      for (int f = 0; f < F; ++f) {
-        const T v = q[(long)f * S + src[i]];
-        if constexpr (G == 2) {
-          const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-          __hip_atomic_store(dst + ring_word(nrec, F * G, rec, 2 * f), tag | (b & 0xFFFFFFFFull), __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_SYSTEM);
-          __hip_atomic_store(dst + ring_word(nrec, F * G, rec, 2 * f + 1), tag | (b >> 32), __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_SYSTEM);
-        } else {
-          __hip_atomic_store(dst + ring_word(nrec, F, rec, f), tag | __builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
-    } else {
-      T* dst = peer_ring[c >> 24] + (long)slot * ring;
-      const int nrec = ring / F, rec = c & 0xFFFFFF;
-      for (int f = 0; f < F; ++f) st_sys(dst + ring_word(nrec, F, rec, f), q[(long)f * S + src[i]]);
-    }
+    if (F == 4) xg_prime_record<XgPlain<T, 4>, 4>(q, S, src[i], code[i], peer_ring, ring, epoch);
+    else xg_prime_record<XgPlain<T, 1>, 1>(q, S, src[i], code[i], peer_ring, ring, epoch);
   }
   __threadfence_system();
 }
@@ -1068,7 +969,7 @@ extern "C" int stsp_copy_index_launch(int dtype, const void* src, const int* sid
 extern "C" int stsp_xg_prime_launch(int dtype, const void* q, int S, int F, const int* src, const int* code, int nent,
                                     void* const* peer_ring, int ring, int epoch, hipStream_t stream) {
   if (nent <= 0) return 0;
-  if (epoch < 0 || ring <= 0) return -6;
+  if (epoch < 0 || ring <= 0 || (F != 1 && F != 4)) return -6;
   const int nb = (nent + 255) / 256;
   if (dtype == 1)
     hipLaunchKernelGGL(xg_prime_kernel<double>, dim3(nb), dim3(256), 0, stream, (const double*)q, S, F, src, code,
@@ -1079,7 +980,6 @@ extern "C" int stsp_xg_prime_launch(int dtype, const void* q, int S, int F, cons
   return (int)hipGetLastError();
 }
 
-extern "C" int stsp_xg_protocol(void) { return STSP_XG_TAG; }
 extern "C" int stsp_xg_slots(void) { return STSP_XG_SLOTS; }
 
 // Threads per stage block as compiled (Geom<BX, BY>::NT; depends on the

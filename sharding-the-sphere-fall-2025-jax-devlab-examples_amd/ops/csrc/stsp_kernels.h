@@ -35,21 +35,16 @@ typedef struct StageDesc {
   void* stamps;         // diagnostic builds only (-DSTSP_STAMPS): [nblocks][16 waves][8] s_memtime per phase
   // ---- direct xGMI halo (xg = 1; see ops/xgmi.py) ----------------------------
   // The producing block stores remote ghost cells straight into the consumer
-  // rank's receive ring (IPC-mapped, uncached, STSP_XG_SLOTS slots).  Protocol
-  // (stsp_xg_protocol()): 1 = tagged granules, every ghost word travels as an
-  // 8-byte {epoch tag, 32-bit payload} atomic store and the consumer re-reads
-  // its granules until every tag matches (no counters, no drain); 0 = arrival
-  // counters (the producer drains its stores and bumps a counter per peer; a
-  // consumer block polls the counters of the peers it reads).
+  // rank's receive ring (IPC-mapped, uncached, STSP_XG_SLOTS slots) as tagged
+  // granules: every ghost word travels as an 8-byte {epoch tag, 32-bit payload}
+  // atomic store and the consumer re-reads its granules until every tag
+  // matches (no counters, no drain; the protocol is xg_ring.h).
   // `recv` is then this rank's ring base; `push` entries < -1 encode
   // -2 - (peer << 24 | slot).
   int xg;
-  int ring;             // per ring slot: elements (counters) or 8-byte granules (tags)
+  int ring;             // 8-byte granules per ring slot
   void* const* peer_ring;                  // [world] ring base of rank p (device array)
-  unsigned long long* const* peer_cnt;     // [world] &counter[my rank] on rank p
-  const unsigned long long* cnt;           // [world] arrival counters on this rank
-  const unsigned long long* nprod;         // [world] producer blocks of rank p feeding this rank
-  const int* bmask;     // [nblocks][2] (peers read, peers fed) bit masks
+  const int* bmask;     // [nblocks][2] (peers read, peers fed) bit masks; the kernel reads the first
   int* epoch;           // [nblocks] stages completed
   int* err;             // set to 1 on a poll timeout (all later polls fall through)
   long long timeout_ticks;  // s_memrealtime ticks (100 MHz)
@@ -213,7 +208,6 @@ typedef struct DerivedDesc {
 } DerivedDesc;
 int stsp_derived_launch(int dtype, const DerivedDesc* d, hipStream_t stream);
 int stsp_derived_desc_size(void);
-// Direct xGMI halo build constants: protocol (0 counters, 1 tagged granules), ring slots.
-int stsp_xg_protocol(void);
+// Direct xGMI halo build constant: ring slots.
 int stsp_xg_slots(void);
 }

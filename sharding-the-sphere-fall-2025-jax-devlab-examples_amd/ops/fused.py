@@ -1285,11 +1285,9 @@ class FusedKernel:
         refuse_if_forced()
         e = self.e
         L = _declare(self.lib)
-        if int(L.stsp_xg_protocol()) != 1:
-            raise RuntimeError("fused multi-rank step needs the tagged-granule protocol (STSP_XG_TAG=1)")
         self._xlib = L
         self.slots = int(L.stsp_xg_slots())
-        # packed cell records (fused_step.hip HX<T>): 5 granules per fp64 cell
+        # packed cell records (xg_codec.h HX<T>): 5 granules per fp64 cell
         self.ring = X.ring_slots * int(self.lib.stsp_fused_record_words(self.dcode))
         xpush, psrc, pcode = X.producer(e.rank)
         assert psrc.size == 0 or int(psrc.max()) < e.plan.S
@@ -1710,7 +1708,7 @@ class FusedExchangePlan:
             tid, i, j = L.locate(g)
             # producer order: owner rank, tile, block row, block column, then
             # the block's cells in row order (the producing wave's lane order),
-            # so the word-major ring (stage_common.h, STSP_XG_SOA) takes a
+            # so the word-major ring (xg_ring.h) takes a
             # wave's pushes to one peer as runs of consecutive 8-byte words
             # (tools/ring_model.py)
             order = np.lexsort((i % B, j % B, i // B, j // B, tid, owner[tid]))

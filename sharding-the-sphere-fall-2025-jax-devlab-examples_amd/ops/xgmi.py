@@ -12,32 +12,23 @@ XG variant).  It is the explicit form of the cross-device transfer the
 reference leaves to XLA when ``exchange_edge_pair`` (PY:166-197) reads one
 sharded face and writes another:
 
-* Every rank owns one uncached allocation holding ``[world]`` u64 arrival
-  counters and a 4-slot receive ring (``ring_slots x F`` values per slot).
-  Peers map it with ``hipIpcOpenMemHandle``.
+* Every rank owns one uncached allocation holding a 4-slot receive ring
+  (``ring_slots`` records of ``F`` values per slot, one 8-byte granule per
+  32-bit word).  Peers map it with ``hipIpcOpenMemHandle``.
 * A block whose cells are ghosts of another rank stores them into that rank's
   ring slot ``(epoch + 1) % 4``.  The push map carries the destination:
   ``-2 - (peer << 24 | slot)``.
-* Hand-off (``stsp_xg_protocol()``, compile-time):
-
-  - tagged granules (1): every 32-bit word of a ghost travels as one 8-byte
-    ``{tag = epoch + 1, payload}`` atomic store; the consumer thread re-reads
-    its granules until every tag matches.  The data is the flag: no drain, no
-    counter, no separate poll round trip.
-  - arrival counters (0): the producer's waves drain their stores, then one
-    lane per peer adds 1 to that peer's counter (system-scope release).  A
-    block that reads remote ghosts polls the counters of those peers until
-    ``counter[p] >= epoch * nprod[p]``.  ``nprod[p]`` is the number of producer
-    blocks on p that feed this rank.
-
-  Either wait is bounded by a timeout that sets ``err``; after that every wait
-  falls through.
-* ``epoch`` is a per-block count of completed stages.  Tags and counters never
-  reset.
+* Hand-off by tagged granules (device side: ``ops/csrc/xg_ring.h``, the one
+  place the protocol lives): every 32-bit word of a ghost travels as one 8-byte
+  ``{tag = epoch + 1, payload}`` atomic store; the consumer thread re-reads
+  its granules until every tag matches.  The data is the flag: no drain, no
+  counter, no separate poll round trip.  The wait is bounded by a timeout that
+  sets ``err``; after that every wait falls through.
+* ``epoch`` is a per-block count of completed stages.  Tags never reset.
 
 Four slots make the ring race-free: a peer can have started at most two stages
-past a rank's current stage (the proof is at STSP_XG_SLOTS in the kernel), so
-it never writes the slot that rank still reads.  The whole step is plain
+past a rank's current stage (the proof is at STSP_XG_SLOTS in ``xg_ring.h``),
+so it never writes the slot that rank still reads.  The whole step is plain
 kernels, so multi-GPU steps are captured in a hipGraph like single-GPU ones.
 
 ``XgmiPlan`` is the host-side index math (numpy only, tested on CPU).
@@ -53,7 +44,6 @@ import torch
 
 from ..parallel.layout import TileLayout, corner_own_index, corner_xy
 
-CNT_BYTES = 256          # counter block at the start of each rank's allocation (<= 32 ranks)
 MAX_WORLD = 32
 SLOT_BITS = 24
 
@@ -251,14 +241,9 @@ class XgmiHalo:
         dev = e.device
         F = e.physics.F
         self.esize = torch.tensor([], dtype=e.dtype).element_size()
-        self.protocol = int(L.stsp_xg_protocol())
         self.slots = int(L.stsp_xg_slots())
-        if self.protocol == 1:   # 8-byte granules, one per 32-bit word
-            self.ring = self.xp.ring_slots * F * (self.esize // 4)
-            nbytes = CNT_BYTES + self.slots * self.ring * 8
-        else:
-            self.ring = self.xp.ring_slots * F
-            nbytes = CNT_BYTES + self.slots * self.ring * self.esize
+        self.ring = self.xp.ring_slots * F * (self.esize // 4)   # 8-byte granules, one per 32-bit word
+        nbytes = self.slots * self.ring * 8
         self.base = None
         peers = sorted(set(self.xp.plan.send_peers) | set(self.xp.plan.recv_peers))
         self.mem = IpcRing(L, dev, world, self.rank, peers, nbytes, group)
@@ -266,13 +251,9 @@ class XgmiHalo:
         bases = self.mem.bases
         distributed = self.mem.distributed
         pr = np.zeros(MAX_WORLD, dtype=np.int64)
-        pc = np.zeros(MAX_WORLD, dtype=np.int64)
         for p, b in bases.items():
-            pr[p] = b + CNT_BYTES
-            pc[p] = b + 8 * self.rank
+            pr[p] = b
         self.peer_ring = torch.as_tensor(pr, device=dev)
-        self.peer_cnt = torch.as_tensor(pc, device=dev)
-        self.nprod = torch.as_tensor(self.xp.nprod, device=dev)
         self.bmask = torch.as_tensor(self.xp.bmask, device=dev)
         # per-block (stage kernel) or per-job (march kernel) stage counts
         assert hc.march or hc.nblocks == self.xp.nblocks
@@ -316,13 +297,10 @@ class XgmiHalo:
         d.blocks = 0
         d.nblocks = self.xp.nblocks
         d.ring = self.ring
-        d.recv = self.base + CNT_BYTES
+        d.recv = self.base
         d.push = native.ptr(self.push)
         d.cpush = native.ptr(self.cpush)
         d.peer_ring = native.ptr(self.peer_ring)
-        d.peer_cnt = native.ptr(self.peer_cnt)
-        d.cnt = self.base
-        d.nprod = native.ptr(self.nprod)
         d.bmask = native.ptr(self.bmask)
         d.epoch = native.ptr(self.epoch)
         d.err = native.ptr(self.err)
@@ -516,8 +494,6 @@ def _declare(L):
     L.stsp_enable_peers.restype = ci
     L.stsp_xg_prime_launch.argtypes = [ci, vp, ci, ci, vp, vp, ci, vp, ci, ci, vp]
     L.stsp_xg_prime_launch.restype = ci
-    L.stsp_xg_protocol.argtypes = []
-    L.stsp_xg_protocol.restype = ci
     L.stsp_xg_slots.argtypes = []
     L.stsp_xg_slots.restype = ci
     return L

@@ -539,9 +539,11 @@ def test_fused_loopback_plan_equals_one_rank_cpu(N, t, B):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("handoff", ["auto", "tag", "epoch"])
-@pytest.mark.parametrize("N,t", [(32, 2), (96, 2), (36, 1)])
-def test_fused_loopback_kernel_equals_one_rank(monkeypatch, N, t, handoff):
+@pytest.mark.parametrize("N,t,handoff,dtype", [
+    pytest.param(N, t, h, torch.float64, id=f"{N}-{t}-{h}")
+    for h in ("auto", "tag", "epoch") for N, t in ((32, 2), (96, 2), (36, 1))
+] + [pytest.param(32, 2, "auto", torch.float32, id="32-2-auto-fp32")])   # fp32: four one-value granules per cell
+def test_fused_loopback_kernel_equals_one_rank(monkeypatch, N, t, handoff, dtype):
     """The gfx950 fused kernel on a loopback layout (the xGMI ring protocol
     through the rank's own ring, tagged granules every step, one and several
     steps per launch; the in-rank cells by either in-launch hand-off) equals
@@ -549,9 +551,9 @@ def test_fused_loopback_kernel_equals_one_rank(monkeypatch, N, t, handoff):
     from stsphere.ops.fused import FusedKernel
     monkeypatch.setenv("STSP_FUSED_HANDOFF", handoff)
     grid = CubedSphereGrid(N)
-    _, a = _gpu_pair(N, t)
+    _, a = _gpu_pair(N, t, dtype=dtype)
     Llb = TileLayout(N, t, 1, ng=2, loopback=True)
-    b = Engine(ShallowWater("tc5"), Llb, grid=grid, dtype=torch.float64, device="cuda", backend="hip", dt=a.dt)
+    b = Engine(ShallowWater("tc5"), Llb, grid=grid, dtype=dtype, device="cuda", backend="hip", dt=a.dt)
     fa = FusedKernel(a)
     fb = FusedKernel(b, B=fa.plan.B)
     assert fb.mem is not None

@@ -37,17 +37,23 @@ def _free_port():
     return p
 
 
-@pytest.mark.parametrize("N,t,integ,use_graph", [(24, 2, "ssprk3", True), (24, 2, "ssprk3", False),
-                                                 (32, 2, "rk4", True), (20, 1, "euler", True),
-                                                 (48, 2, "ssprk2", True)])
-def test_xgmi_loopback_matches_single(N, t, integ, use_graph):
+# (the fp32 case is the only run of the stage kernel's one-granule-per-value records through the ring)
+@pytest.mark.parametrize("N,t,integ,use_graph,dtype", [
+    pytest.param(24, 2, "ssprk3", True, torch.float64, id="24-2-ssprk3-True"),
+    pytest.param(24, 2, "ssprk3", False, torch.float64, id="24-2-ssprk3-False"),
+    pytest.param(32, 2, "rk4", True, torch.float64, id="32-2-rk4-True"),
+    pytest.param(20, 1, "euler", True, torch.float64, id="20-1-euler-True"),
+    pytest.param(48, 2, "ssprk2", True, torch.float64, id="48-2-ssprk2-True"),
+    pytest.param(24, 2, "ssprk3", True, torch.float32, id="24-2-ssprk3-True-fp32")])
+def test_xgmi_loopback_matches_single(N, t, integ, use_graph, dtype):
     from stsphere.ops.native_runtime import NativeStepper
     from stsphere.ops.xgmi import XgmiHalo
     g = CubedSphereGrid(N)
-    a = Engine(ShallowWater("tc5"), TileLayout(N, t, 1, ng=2), grid=g, device="cuda", backend="hip", integrator=integ)
+    a = Engine(ShallowWater("tc5"), TileLayout(N, t, 1, ng=2), grid=g, device="cuda", backend="hip", integrator=integ,
+               dtype=dtype)
     L = TileLayout(N, t, 1, ng=2, loopback=True)
-    b = Engine(ShallowWater("tc5"), L, grid=g, device="cuda", backend="hip", integrator=integ, dt=a.dt,
-               transport=NativeBuffers(L.plan(0), 4, torch.float64, torch.device("cuda")))
+    b = Engine(ShallowWater("tc5"), L, grid=g, device="cuda", backend="hip", integrator=integ, dt=a.dt, dtype=dtype,
+               transport=NativeBuffers(L.plan(0), 4, dtype, torch.device("cuda")))
     xg = XgmiHalo(b, timeout_s=1.0)
     ns = NativeStepper(b, use_graph=use_graph, steps_per_graph=4, xgmi=xg)
     a.step(12)

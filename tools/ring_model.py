@@ -1,9 +1,9 @@
 """Count what the xGMI ring costs per step, from the host plans (no GPU): the
 records each rank pushes, the ring bytes, the wave-level store instructions,
 and the 64-byte memory transactions those instructions touch under the
-record-major layout of round 5 (``aos``: word w of record r at r NW + w) and
-the word-major layout (``soa``: w nrec + r, ops/csrc/stage_common.h
-STSP_XG_SOA), for the fused step (lanes = a block's cells in row order,
+record-major layout of round 5 (``aos``: word w of record r at r NW + w; a
+model only, the kernels no longer build it) and the word-major layout the
+kernels use (``soa``: w nrec + r, ops/csrc/xg_ring.h), for the fused step (lanes = a block's cells in row order,
 ``xpush``) and the streaming march (lanes = 64 consecutive columns of a row,
 the push map).  Input to the 8-GPU step model in docs/ARCHITECTURE.md.
 
