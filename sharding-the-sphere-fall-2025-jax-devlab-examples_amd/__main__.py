@@ -7,8 +7,11 @@
     info CONFIG.yaml                                   validate config, print sharding + halo plan
     schedule                                           print the reference 4-stage halo schedule
     roofline                                           slide-19 roofline / TT model for MI355X
-    plot HISTORY.zarr FIELD OUTDIR [--log] [--products frames,band,six] [--every K]
-                                                       sphere frames, equatorial band, six-panel
+    plot HISTORY.zarr FIELD OUTDIR [--log] [--products frames,band,six] [--every K] [--latlon NLAT NLON]
+                                                       sphere frames, equatorial band, six-panel;
+                                                       --latlon: regridded image + zonal-mean profile
+    regrid HISTORY.zarr FIELD NLAT NLON OUT.npz        regrid a history field (or u, v of a shallow-water
+                                                       history) to the cell-centred lat-lon grid, on the CPU
     ensemble CONFIG.yaml [--members M] [--amplitude A] [--days D | --nsteps K]
                                                        perturbed members of one config on one device
     build                                              compile the gfx950 library
@@ -43,6 +46,14 @@ def main(argv=None):
     p.add_argument("--log", action="store_true")
     p.add_argument("--products", default="frames,band,six")
     p.add_argument("--every", type=int, default=1)
+    p.add_argument("--latlon", type=int, nargs=2, metavar=("NLAT", "NLON"), default=None,
+                   help="also write the last frame regridded to NLAT x NLON with its zonal-mean profile")
+    rg = sub.add_parser("regrid")
+    rg.add_argument("history")
+    rg.add_argument("field")
+    rg.add_argument("nlat", type=int)
+    rg.add_argument("nlon", type=int)
+    rg.add_argument("out")
     en = sub.add_parser("ensemble")
     en.add_argument("config")
     en.add_argument("--members", type=int, default=2)
@@ -71,6 +82,18 @@ def main(argv=None):
         for f in history_products(a.history, a.field, a.outdir, log=a.log, every=a.every,
                                   products=tuple(a.products.split(","))):
             print(f)
+        if a.latlon:
+            from .utils.viz import latlon_image
+            r = regrid_history(a.history, a.field, a.latlon[0], a.latlon[1])
+            os.makedirs(a.outdir, exist_ok=True)
+            print(latlon_image(r["field"][-1], r["lat"], r["lon"], os.path.join(a.outdir, f"{a.field}_latlon.png"),
+                               title=f"{a.field}, day {r['time'][-1] / 86400.0:.2f}", zonal=r["zonal_mean"][-1]))
+        return 0
+    if a.cmd == "regrid":
+        import numpy as np
+        r = regrid_history(a.history, a.field, a.nlat, a.nlon)
+        np.savez(a.out, **r)
+        print(json.dumps({"out": a.out, "field": a.field, "shape": list(r["field"].shape)}))
         return 0
     if a.cmd == "ensemble":
         print(json.dumps(run_ensemble(a.config, a.members, a.amplitude, a.days, a.nsteps), default=float))
@@ -129,6 +152,32 @@ def main(argv=None):
                     print(f)
             print(sphere_plot(g[0], s.grid, os.path.join(out, f"{s.fields[0]}_final.png"), log=log))
     return 0
+
+
+def regrid_history(history: str, field: str, nlat: int, nlon: int) -> dict:
+    """Every frame of a history field on the cell-centred nlat x nlon grid
+    (``u`` / ``v``: from the h, mx, my, mz of a shallow-water history), with the
+    PyTorch twin on the CPU: field [frames, nlat, nlon], zonal_mean [frames,
+    nlat], lat, lon (radians), time."""
+    import numpy as np
+    import torch
+    from .models import latlon as ml
+    from .utils import zarr_lite
+    have = zarr_lite.list_arrays(history)
+    wind = field in ("u", "v") and field not in have
+    need = ["h", "mx", "my", "mz"] if wind else [field]
+    missing = [f for f in need if f not in have]
+    if missing:
+        raise ValueError(f"{history}: no array {missing} (it holds {[f for f in have if f not in ('time', 'step')]})")
+    src = np.stack([zarr_lite.read_array(history, f) for f in need], 1)       # [frames, C, 6, N, N]
+    lat, lon = ml.default_grid(nlat, nlon)
+    tb = ml.regrid_tables(ml.tables_for(src.shape[-1], lat, lon))
+    out = []
+    for fr in torch.as_tensor(np.ascontiguousarray(src, dtype=np.float64)):
+        out.append(ml.winds(fr[0], fr[1:4], tb)[("u", "v").index(field)] if wind else ml.regrid(fr, tb)[0])
+    out = torch.stack(out)
+    return {"field": out.numpy(), "zonal_mean": ml.zonal_mean(out).numpy(), "lat": lat, "lon": lon,
+            "time": zarr_lite.read_array(history, "time")}
 
 
 def run_ensemble(config, members: int, amplitude: float, days=None, nsteps=None) -> dict:

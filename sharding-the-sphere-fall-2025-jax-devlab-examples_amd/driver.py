@@ -42,11 +42,13 @@ from .parallel.layout import TileLayout
 from .parallel.mesh import setup_sharding
 from .utils import checkpoint as ckpt
 from .utils.config import Config, default_case, load_config
-from .utils.history import HistoryWriter, MetricsLogger
+from .utils.history import HistoryWriter, LatLonHistoryWriter, MetricsLogger
 
 
 # invariants the metrics records gain with the shallow-water model
 METRIC_INVARIANTS = ("potential_enstrophy", "circulation", "max_courant")
+# zonal and meridional wind of the lat-lon output (shallow water)
+LATLON_WINDS = ("u", "v")
 
 
 def make_physics(pc) -> Any:
@@ -236,6 +238,10 @@ class Solver:
             if phys0.name != "swe" and any(f in DERIVED_FIELDS for f in hf):
                 raise ValueError(f"io.history_fields: derived fields {list(DERIVED_FIELDS)} need the "
                                  f"shallow-water model, not {phys0.name!r}")
+        ll = c.io.latlon
+        if ll is not None and not (isinstance(ll, (list, tuple)) and len(ll) == 2
+                                   and all(isinstance(v, int) and v > 0 for v in ll)):
+            raise ValueError(f"io.latlon: [nlat, nlon] of two positive integers expected, not {ll!r}")
         self._log(f"Initialized {phys0.name} ({getattr(phys0, 'case', '')}) C{N}, {self.mode} mode, "
                   f"backend={backend}, dtype={c.grid.dtype}, dt={dt:.3f} s, integrator={c.time.integrator}")
         if c.io.initial_condition and not c.io.restore:
@@ -372,6 +378,71 @@ class Solver:
             if self.rank != 0:
                 return None
         return assemble_global(self.layout, vals)
+
+    # ---- lat-lon output (models/latlon.py, ops/latlon.py) ---------------------------
+    def latlon_names(self) -> List[str]:
+        """What ``latlon_field`` / ``zonal_mean`` accept for this model."""
+        swe = self.physics.name == "swe"
+        return list(self.fields) + (list(DERIVED_FIELDS) + list(LATLON_WINDS) if swe else [])
+
+    def _latlon_arrays(self, names, nlat: int, nlon: int, der=None):
+        """(arrays [len(names), nlat, nlon], zonal means [len(names), nlat]
+        float64) of the current state on rank 0, None elsewhere: tensors on the
+        device (single, virtual) or on the CPU (spmd).  Several ranks gather the
+        terms of their own cells, the arrays are added in ascending rank order
+        (virtual ranks on the device, SPMD ranks on rank 0 after an
+        ``all_gather_object``) and the finish step runs on the sum: the one-rank
+        result bit for bit.  ``der``: the engines' derived fields when the
+        caller has them already (``_derived_all()``).  Collective under SPMD."""
+        for name in names:
+            if name in DERIVED_FIELDS or name in LATLON_WINDS:
+                if self.physics.name != "swe":
+                    kind = "derived fields" if name in DERIVED_FIELDS else "winds"
+                    raise ValueError(f"{kind} are defined for the shallow-water model, not {self.physics.name!r}")
+            elif name not in self.fields:
+                raise ValueError(f"unknown lat-lon field {name!r}; choose from {self.latlon_names()}")
+        lls = [e.latlon(nlat=nlat, nlon=nlon) for e in self.engines]
+        groups = []
+        terms = self.layout.num_ranks > 1
+        if any(f in self.fields for f in names):
+            groups.append(("prog", [ll.partial_fields(terms=terms) for ll in lls], False))
+        if any(f in DERIVED_FIELDS for f in names):
+            der = self._derived_all() if der is None else der
+            groups.append(("der", [ll.partial_tiles(f, terms=terms) for ll, (f, _) in zip(lls, der)], False))
+        if any(f in LATLON_WINDS for f in names):
+            groups.append(("wind", [ll.partial_velocity(terms=terms) for ll in lls], True))
+        done = {}
+        for kind, parts, project in groups:
+            if self.mode == "spmd":
+                import torch.distributed as dist
+                objs = [None] * self.world
+                dist.all_gather_object(objs, (self.rank, parts[0].detach().cpu().numpy()))
+                if self.rank != 0:
+                    continue
+                parts = [torch.as_tensor(a) for _, a in sorted(objs, key=lambda o: o[0])]
+            done[kind] = lls[0].finish(lls[0].add_partials(parts).contiguous(), project=project)
+        if self.rank != 0:
+            return None
+        rows, zms = [], []
+        for name in names:
+            kind, k = (("prog", self.fields.index(name)) if name in self.fields else
+                       ("der", DERIVED_FIELDS.index(name)) if name in DERIVED_FIELDS else
+                       ("wind", LATLON_WINDS.index(name)))
+            rows.append(done[kind][0][k])
+            zms.append(done[kind][1][k])
+        return torch.stack(rows), torch.stack(zms)
+
+    def latlon_field(self, name: str, nlat: int, nlon: int) -> Optional[np.ndarray]:
+        """[nlat, nlon] of a prognostic field, ``vorticity``, ``divergence``,
+        ``pv``, ``u`` or ``v`` on the cell-centred lat-lon grid, on rank 0 (None
+        elsewhere), like ``global_field``."""
+        r = self._latlon_arrays([name], nlat, nlon)
+        return None if r is None else r[0][0].detach().cpu().double().numpy()
+
+    def zonal_mean(self, name: str, nlat: int, nlon: int) -> Optional[np.ndarray]:
+        """[nlat] zonal mean of ``latlon_field(name, nlat, nlon)``."""
+        r = self._latlon_arrays([name], nlat, nlon)
+        return None if r is None else r[1][0].detach().cpu().numpy()
 
     def invariants(self) -> Dict[str, float]:
         """mass, energy, potential_enstrophy, circulation, abs_circulation
@@ -634,6 +705,16 @@ class Solver:
                               attrs={"config": self.config}, frame_chunks=self.mode != "spmd")
             self._barrier()
             hist = HistoryWriter(hpath, hfields, self.layout.N, self.layout.n, n_out, create=False)
+            if io.latlon is not None:
+                # the same frames on the lat-lon grid: the selected fields, or the
+                # prognostic ones plus the winds of the shallow-water model
+                lfields = list(hfields) if io.history_fields is not None else (
+                    self.fields + (list(LATLON_WINDS) if self.physics.name == "swe" else []))
+                if self.rank == 0:
+                    hll = LatLonHistoryWriter(os.path.join(out, "history_latlon.zarr"), lfields, io.latlon[0],
+                                              io.latlon[1], n_out, attrs={"config": self.config, "N": self.layout.N})
+        # (writer on rank 0, names) of the lat-lon frames; None: io.latlon unset
+        self._latlon_hist = (hll if self.rank == 0 else None, lfields) if hist is not None and io.latlon else None
         metrics = MetricsLogger(os.path.join(out, "metrics.jsonl") if "metrics" in iv else None,
                                 enabled=self.rank == 0)
         cells = 6 * self.layout.N ** 2
@@ -801,6 +882,31 @@ class Solver:
                 hist.write_tiles(k, tiles, self.layout.tile_origin, arr)
             if self.rank == 0:
                 hist.write_time(k, t, sc)
+        pending.append((ev, work))
+        if getattr(self, "_latlon_hist", None) is not None:
+            self._snapshot_latlon(*self._latlon_hist, k, pending, async_copy, der)
+
+    def _snapshot_latlon(self, hll, names, k: int, pending: List[Any], async_copy: bool, der=None) -> None:
+        """Lat-lon arrays of history frame k (``io.latlon``): computed on the
+        stepping stream, copied to pinned host memory there and written by the
+        host queue like the frame itself.  Collective under SPMD."""
+        t, sc = self.time, self.step_count
+        nlat, nlon = self.cfg.io.latlon
+        r = self._latlon_arrays(names, nlat, nlon, der=der)
+        if r is None:
+            return
+        v = r[0].detach()
+        ev = None
+        if async_copy and v.is_cuda:
+            h = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
+            h.copy_(v, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        else:
+            h = v.cpu()
+
+        def work():
+            hll.write_frame(k, h.double().numpy(), t, sc)
         pending.append((ev, work))
 
     def _snapshot_metrics(self, metrics: MetricsLogger, pending: List[Any], deferred: bool, cells: int,

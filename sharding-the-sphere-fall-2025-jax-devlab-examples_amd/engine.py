@@ -90,6 +90,7 @@ class Engine:
         self.time = 0.0
         self.step_count = 0
         self.backend = backend
+        self._latlon: Dict[tuple, object] = {}      # ops.latlon.LatLon per target grid (latlon())
         self.block = tuple(block) if block is not None else None   # None: ops.hip_compute.choose_block
         if backend == "torch":
             self.compute = TorchCompute(self)
@@ -221,6 +222,23 @@ class Engine:
         from .models.derived import INVARIANTS
         inv = self.derived(exchange)[1]
         return dict(zip(INVARIANTS, inv.tolist()))
+
+    def latlon(self, lat=None, lon=None, nlat: Optional[int] = None, nlon: Optional[int] = None):
+        """``ops.latlon.LatLon`` of this engine for the target grid ``lat`` /
+        ``lon`` (radians, ascending; default: the cell-centred ``nlat`` x
+        ``nlon`` grid), built on first use and cached per grid."""
+        from .models.latlon import default_grid
+        from .ops.latlon import LatLon
+        if lat is None or lon is None:
+            if nlat is None or nlon is None:
+                raise ValueError("latlon: give lat and lon, or nlat and nlon")
+            lat, lon = default_grid(int(nlat), int(nlon))
+        lat = np.ascontiguousarray(lat, dtype=np.float64)
+        lon = np.ascontiguousarray(lon, dtype=np.float64)
+        key = (lat.tobytes(), lon.tobytes())
+        if key not in self._latlon:
+            self._latlon[key] = LatLon(self, lat, lon)
+        return self._latlon[key]
 
     def global_field(self, f: int = 0) -> np.ndarray:
         """Single-rank only: [6, N, N] float64 of field f."""

@@ -208,6 +208,31 @@ typedef struct DerivedDesc {
 } DerivedDesc;
 int stsp_derived_launch(int dtype, const DerivedDesc* d, hipStream_t stream);
 int stsp_derived_desc_size(void);
+// Longitude-latitude regridding (latlon_kernel.hip, ops/latlon.py; definitions
+// and tables in models/latlon.py): a gather launch (one thread per target
+// point) and a finish launch (projection onto east / north, zonal means; one
+// workgroup per latitude row).  `phases` selects them: with several ranks the
+// caller adds the ranks' term arrays (`terms`) between the two.
+typedef struct LatLonDesc {
+  const void* Q;        // source channels [C][cs]; velocity: h, then M (3) at stride cs
+  const int* idx;       // [K][4] source index inside a channel, -1 = skipped (16-byte aligned)
+  const double* w;      // [K][4] weights (32-byte aligned)
+  const double* east;   // [K][3] unit east vectors (project)
+  const double* north;  // [K][3]
+  void* partial;        // gather out / finish in, element type: [C][K], or the four terms of each sum
+                        // [C][4][K] (terms); K = nlat nlon, k = j nlon + i
+  void* out;            // finish out, element type: [2][K] (project) or the folded [C][K] (terms)
+  double* zm;           // finish out: zonal means [C][nlat] ([2][nlat] with project; nullable then)
+  long long cs;         // channel stride of Q in elements
+  int K, nlat, nlon;
+  int C;                // channels (3 with velocity / project)
+  int velocity;         // gather: 1 = v = M / h per source cell
+  int project;          // finish: 1 = (u, v) from the Cartesian triple
+  int phases;           // bit 0 gather, bit 1 finish
+  int terms;            // 1 = partial holds the unsummed terms (several ranks)
+} LatLonDesc;
+int stsp_latlon_launch(int dtype, const LatLonDesc* d, hipStream_t stream);
+int stsp_latlon_desc_size(void);
 // Direct xGMI halo build constant: ring slots.
 int stsp_xg_slots(void);
 }

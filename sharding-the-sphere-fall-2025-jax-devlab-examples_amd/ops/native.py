@@ -95,6 +95,19 @@ class DerivedDesc(ctypes.Structure):
     ]
 
 
+class LatLonDesc(ctypes.Structure):
+    """Mirror of LatLonDesc (stsp_kernels.h): lat-lon regridding."""
+    _fields_ = [
+        ("Q", ctypes.c_void_p), ("idx", ctypes.c_void_p), ("w", ctypes.c_void_p),
+        ("east", ctypes.c_void_p), ("north", ctypes.c_void_p),
+        ("partial", ctypes.c_void_p), ("out", ctypes.c_void_p), ("zm", ctypes.c_void_p),
+        ("cs", ctypes.c_longlong),
+        ("K", ctypes.c_int), ("nlat", ctypes.c_int), ("nlon", ctypes.c_int), ("C", ctypes.c_int),
+        ("velocity", ctypes.c_int), ("project", ctypes.c_int), ("phases", ctypes.c_int),
+        ("terms", ctypes.c_int),
+    ]
+
+
 def lib_path() -> str:
     return _build.lib_for(os.environ.get("STSP_VARIANT", ""))
 
@@ -142,6 +155,13 @@ def load(build_if_missing: bool = True):
         if L.stsp_derived_desc_size() != ctypes.sizeof(DerivedDesc):
             raise RuntimeError(f"DerivedDesc: ctypes mirror is {ctypes.sizeof(DerivedDesc)} bytes, "
                                f"the library's {L.stsp_derived_desc_size()} (stale libstsp.so?)")
+        L.stsp_latlon_launch.argtypes = [ci, ctypes.POINTER(LatLonDesc), vp]
+        L.stsp_latlon_launch.restype = ci
+        L.stsp_latlon_desc_size.argtypes = []
+        L.stsp_latlon_desc_size.restype = ci
+        if L.stsp_latlon_desc_size() != ctypes.sizeof(LatLonDesc):
+            raise RuntimeError(f"LatLonDesc: ctypes mirror is {ctypes.sizeof(LatLonDesc)} bytes, "
+                               f"the library's {L.stsp_latlon_desc_size()} (stale libstsp.so?)")
         _declare_runtime(L)
         _declare_tt(L)
         L.stsp_schedule_spin.argtypes = [ci]

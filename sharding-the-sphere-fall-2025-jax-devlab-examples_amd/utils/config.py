@@ -77,6 +77,9 @@ class IOConfig:
     # jax.zarr"): a zarr group written on the first run, read when present
     geometry: Optional[str] = None
     initial_condition: Optional[str] = None
+    # [nlat, nlon]: every history frame is also written on the cell-centred
+    # lat-lon grid, to history_latlon.zarr (models/latlon.py); null = off
+    latlon: Optional[List[int]] = None
 
 
 @dataclass

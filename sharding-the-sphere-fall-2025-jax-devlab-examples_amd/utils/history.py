@@ -76,6 +76,43 @@ class HistoryWriter:
         zarr_lite.write_chunk(self.path, "step", (0,), self._steps, meta=self._meta["step"])
 
 
+class LatLonHistoryWriter:
+    """History frames on a cell-centred lat-lon grid (``io.latlon``):
+
+        history_latlon.zarr/<field>   shape (n_out, nlat, nlon), chunks (1, nlat, nlon)
+        history_latlon.zarr/lat, lon  radians
+        history_latlon.zarr/time, step
+
+    written whole, frame by frame, by rank 0."""
+
+    def __init__(self, path: str, fields: List[str], nlat: int, nlon: int, n_out: int,
+                 attrs: Optional[Dict[str, Any]] = None):
+        from ..models.latlon import default_grid
+        self.path, self.fields, self.n_out = path, list(fields), n_out
+        zarr_lite.create_group(path, attrs=dict(attrs or {}, fields=self.fields, nlat=nlat, nlon=nlon))
+        for f in self.fields:
+            zarr_lite.create_array(path, f, (n_out, nlat, nlon), np.float64, chunks=(1, nlat, nlon))
+        lat, lon = default_grid(nlat, nlon)
+        zarr_lite.write_array(path, "lat", lat)
+        zarr_lite.write_array(path, "lon", lon)
+        zarr_lite.create_array(path, "time", (n_out,), np.float64, chunks=(n_out,))
+        zarr_lite.create_array(path, "step", (n_out,), np.int64, chunks=(n_out,))
+        self._meta = {f: zarr_lite.array_meta(path, f) for f in self.fields + ["time", "step"]}
+        self._times = np.zeros(n_out)
+        self._steps = np.zeros(n_out, dtype=np.int64)
+
+    def write_frame(self, k: int, values: np.ndarray, t: float, step: int) -> None:
+        """values [len(fields), nlat, nlon] for history slot k."""
+        if k >= self.n_out:
+            return
+        for j, name in enumerate(self.fields):
+            zarr_lite.write_chunk(self.path, name, (k, 0, 0), values[j][None], meta=self._meta[name])
+        self._times[k] = t
+        self._steps[k] = step
+        zarr_lite.write_chunk(self.path, "time", (0,), self._times, meta=self._meta["time"])
+        zarr_lite.write_chunk(self.path, "step", (0,), self._steps, meta=self._meta["step"])
+
+
 def read_history(path: str, field: str) -> np.ndarray:
     return zarr_lite.read_array(path, field)
 

@@ -5,6 +5,8 @@ s.4, s.12, s.13, s.17, s.18).
                     colour scale (Lima-flag diffusion, PDF s.12 / s.17)
 * ``latlon_band``   longitude-latitude scatter of a band, e.g. 0-360 x +-50 deg
                     (cosine bell, PDF s.13)
+* ``latlon_image``  image of a field regridded to a lat-lon grid (models/latlon.py)
+                    beside its zonal-mean profile
 * ``six_panel``     per-face images of an initial and a final field
                     (PDF s.18 "Initial vs Final")
 * ``mesh_plot``     the cubed-sphere dual mesh outline (PDF s.4)
@@ -64,6 +66,28 @@ def latlon_band(field: np.ndarray, grid: CubedSphereGrid, path: str, lat_max_deg
     ax.set_ylabel("latitude (deg)")
     ax.set_title(title or f"peak {v.max():.1f}")
     fig.colorbar(sc, ax=ax)
+    fig.savefig(path, dpi=110, bbox_inches="tight")
+    plt.close(fig)
+    return path
+
+
+def latlon_image(arr: np.ndarray, lat: np.ndarray, lon: np.ndarray, path: str, title: str = "",
+                 cmap: str = "viridis", zonal: Optional[np.ndarray] = None) -> str:
+    """Image of a regridded [nlat, nlon] array (lat, lon in radians) with its
+    zonal-mean profile (``zonal`` [nlat]; default: the row means) to the right."""
+    plt = _plt()
+    arr = np.asarray(arr)
+    latd, lond = np.degrees(np.asarray(lat)), np.degrees(np.asarray(lon))
+    zonal = arr.mean(1) if zonal is None else np.asarray(zonal)
+    fig, (ax, az) = plt.subplots(1, 2, figsize=(11, 3.8), sharey=True, gridspec_kw={"width_ratios": [5, 1]})
+    im = ax.pcolormesh(lond, latd, arr, cmap=cmap, shading="nearest")
+    ax.set_xlabel("longitude (deg E)")
+    ax.set_ylabel("latitude (deg)")
+    ax.set_title(title)
+    fig.colorbar(im, ax=ax, pad=0.02)
+    az.plot(zonal, latd, color="k", lw=1.0)
+    az.set_xlabel("zonal mean")
+    az.grid(alpha=0.3)
     fig.savefig(path, dpi=110, bbox_inches="tight")
     plt.close(fig)
     return path
