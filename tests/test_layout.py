@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from stsphere.models.geometry import CubedSphereGrid
-from stsphere.parallel.layout import TileLayout, ghost_xy
+from stsphere.parallel.layout import TileLayout, corner_xy, ghost_xy
 
 
 def _cell_vertex_sets(N):
@@ -129,3 +129,66 @@ def test_block_classes_partition_all_blocks():
     inter, bnd = p.block_classes(16, 16)
     allb = np.sort(np.concatenate([inter, bnd]))
     assert (allb == np.arange(p.T * 2 * 2)).all() and len(bnd) > 0 and len(inter) > 0
+
+
+PPM_BLOCKS = [(16, 16), (16, 8), (8, 16), (32, 8)]
+WINDOW_LAYOUTS = [(24, 2, 4, False), (34, 1, 2, False), (36, 2, 8, False), (48, 1, 6, False), (36, 3, 6, False),
+                  (24, 2, 1, True)]
+# interior blocks over all ranks, 16 x 16 blocks, counted by hand from the geometry:
+# (34,1,2): blocks at 0, 16, 32; the window of block 1 spans 13 .. 34 with three layers
+# (reaches the far strip) and 14 .. 33 with two (does not)
+INTERIOR_16x16 = {(34, 1, 2, 3): 12, (48, 1, 6, 3): 6, (24, 2, 4, 3): 0, (24, 2, 4, 2): 0, (48, 1, 6, 2): 6}
+
+
+def _window_reads_remote(plan, t, x0, y0, bx, by, ng, corners):
+    """The stage kernel's window of one block, cell by cell, bounded as its
+    loader bounds it (x < n + ng and y < n + ng): does any cell come out of
+    the receive buffer?"""
+    n = plan.n
+    for Y in range(y0 - ng, min(y0 + by + ng, n + ng)):
+        for X in range(x0 - ng, min(x0 + bx + ng, n + ng)):
+            ox, oy = X < 0 or X >= n, Y < 0 or Y >= n
+            if ox and oy:
+                if (X, Y) in corners:
+                    return True
+            elif ox:
+                if plan.ghost_map[t, 0 if X < 0 else 1, -1 - X if X < 0 else X - n, Y] < 0:
+                    return True
+            elif oy:
+                if plan.ghost_map[t, 2 if Y < 0 else 3, -1 - Y if Y < 0 else Y - n, X] < 0:
+                    return True
+    return False
+
+
+@pytest.mark.parametrize("bx,by", PPM_BLOCKS)
+@pytest.mark.parametrize("N,t,R,loop", WINDOW_LAYOUTS)
+@pytest.mark.parametrize("ng", [2, 3])
+def test_block_classes_match_the_window_replay(ng, N, t, R, loop, bx, by):
+    """Every block whose (bx + 2 ng) x (by + 2 ng) window touches a remote strip
+    cell or a remote carried corner waits for the exchange (boundary class);
+    a block that touches neither is not held back (interior class)."""
+    L = TileLayout(N, t, R, ng=ng, loopback=loop)
+    n = L.n
+    nbx, nby = -(-n // bx), -(-n // by)
+    ninterior = 0
+    for r in range(R):
+        plan = L.plan(r)
+        inter, bnd = plan.block_classes(bx, by)
+        assert (np.sort(np.concatenate([inter, bnd])) == np.arange(plan.T * nbx * nby)).all()
+        bnd = set(bnd.tolist())
+        rc = plan.remote_corners()
+        free = 0
+        for tl in range(plan.T):
+            q, a, b = np.nonzero(rc[tl])
+            corners = set(zip(*(v.tolist() for v in corner_xy(q, a, b, n))))
+            for yb in range(nby):
+                for xb in range(nbx):
+                    bid = (tl * nby + yb) * nbx + xb
+                    if _window_reads_remote(plan, tl, xb * bx, yb * by, bx, by, ng, corners):
+                        assert bid in bnd, (r, tl, yb, xb)
+                    else:
+                        free += 1
+        assert (len(inter) > 0) == (free > 0) and len(inter) <= free, (r, len(inter), free)
+        ninterior += len(inter)
+    if (bx, by) == (16, 16) and (N, t, R, ng) in INTERIOR_16x16:
+        assert ninterior == INTERIOR_16x16[(N, t, R, ng)]

@@ -21,7 +21,13 @@ pytestmark = pytest.mark.gpu
 
 def _single(N=24, t=2, phys=lambda: ShallowWater("tc5"), integ="ssprk3"):
     g = CubedSphereGrid(N)
-    return g, Engine(phys(), TileLayout(N, t, 1, ng=2), grid=g, device="cuda", backend="hip", integrator=integ)
+    return g, Engine(phys(), TileLayout(N, t, 1, ng=phys().halo), grid=g, device="cuda", backend="hip", integrator=integ)
+
+
+# the physics of the loopback transports: MC-limited (two ghost layers), and PPM
+# (limiter 4) with three layers and 3 x 3 carried corners in every message
+MK = {"swe": lambda: ShallowWater("tc5"), "adv": lambda: Advection(),
+      "swe_ppm": lambda: ShallowWater("tc5", limiter=4), "adv_ppm": lambda: Advection(limiter=4)}
 
 
 @pytest.mark.parametrize("use_graph", [True, False])
@@ -108,10 +114,20 @@ def test_rccl_selftest(nccl_comm):
 @pytest.mark.parametrize("use_graph", [False, True])
 @pytest.mark.parametrize("phys", ["swe", "adv"])
 def test_rccl_loopback_full_multigpu_path(nccl_comm, use_graph, phys):
+    _rccl_loopback(nccl_comm, use_graph, phys)
+
+
+@pytest.mark.parametrize("phys", ["swe_ppm", "adv_ppm"])
+def test_rccl_loopback_full_multigpu_path_ppm(nccl_comm, phys):
+    """Three ghost layers through pack -> RCCL -> the receive-buffer gather of the PPM stage kernel."""
+    _rccl_loopback(nccl_comm, False, phys)
+
+
+def _rccl_loopback(nccl_comm, use_graph, phys):
     from stsphere.ops.native_runtime import NativeStepper
-    mk = {"swe": lambda: ShallowWater("tc5"), "adv": lambda: Advection()}[phys]
+    mk = MK[phys]
     g, ref = _single(phys=mk)
-    L = TileLayout(24, 2, 1, ng=2, loopback=True)
+    L = TileLayout(24, 2, 1, ng=mk().halo, loopback=True)
     p = L.plan(0)
     F = ref.physics.F
     e = Engine(mk(), L, grid=g, device="cuda", backend="hip", dt=ref.dt,
@@ -128,6 +144,12 @@ def test_rccl_loopback_full_multigpu_path(nccl_comm, use_graph, phys):
 
 
 @pytest.mark.parametrize("use_graph", [True, False])
+def test_ipc_copy_loopback_full_multigpu_path_ppm(use_graph):
+    """PPM: three layers and the carried corners in one copy per stage."""
+    _ipc_loopback(use_graph, "ssprk3", "swe_ppm")
+
+
+@pytest.mark.parametrize("use_graph", [True, False])
 @pytest.mark.parametrize("integ", ["ssprk3", "rk4"])
 def test_ipc_copy_loopback_full_multigpu_path(use_graph, integ):
     """The IPC copy transport (pack -> one copy kernel into the peer's receive
@@ -135,11 +157,16 @@ def test_ipc_copy_loopback_full_multigpu_path(use_graph, integ):
     kernel -> boundary blocks) on the loopback layout, where every ghost
     crosses it: bitwise equal to the single-rank engine, and, unlike the RCCL
     op list, recorded into a graph and replayed."""
+    _ipc_loopback(use_graph, integ, "swe")
+
+
+def _ipc_loopback(use_graph, integ, phys):
     from stsphere.ops.native_runtime import IpcExchange, NativeStepper
-    g, ref = _single(integ=integ)
-    L = TileLayout(24, 2, 1, ng=2, loopback=True)
+    mk = MK[phys]
+    g, ref = _single(integ=integ, phys=mk)
+    L = TileLayout(24, 2, 1, ng=mk().halo, loopback=True)
     p = L.plan(0)
-    e = Engine(ShallowWater("tc5"), L, grid=g, device="cuda", backend="hip", dt=ref.dt, integrator=integ,
+    e = Engine(mk(), L, grid=g, device="cuda", backend="hip", dt=ref.dt, integrator=integ,
                transport=NativeBuffers(p, 4, torch.float64, torch.device("cuda")))
     assert e.compute.remote and e.compute.blk_boundary.numel() > 0
     ipc = IpcExchange(e, IpcExchange.slots_for(e))
@@ -156,18 +183,20 @@ def test_ipc_copy_loopback_full_multigpu_path(use_graph, integ):
     ipc.close()
 
 
-@pytest.mark.parametrize("phys,dtype", [("adv", torch.float32), ("adv", torch.float64), ("swe", torch.float32)])
+@pytest.mark.parametrize("phys,dtype", [("adv", torch.float32), ("adv", torch.float64), ("swe", torch.float32),
+                                        ("adv_ppm", torch.float32), ("swe_ppm", torch.float32)])
 def test_ipc_copy_kernel_word_sizes(phys, dtype):
     """The IPC copy kernel (runtime.cpp::ipc_copy_signal_kernel) copies
     16-byte words when every payload allows, else 4-byte words: one field in
     fp32 (tracer advection) gives payloads that are not 16-byte multiples.
     Each case is bitwise equal to the single-rank engine of the same dtype,
-    graph-replayed."""
+    graph-replayed.  The PPM cases carry three layers per strip."""
     from stsphere.ops.native_runtime import IpcExchange, NativeStepper
-    mk = {"swe": lambda: ShallowWater("tc5"), "adv": lambda: Advection()}[phys]
+    mk = MK[phys]
+    ng = mk().halo
     g = CubedSphereGrid(24)
-    ref = Engine(mk(), TileLayout(24, 2, 1, ng=2), grid=g, dtype=dtype, device="cuda", backend="hip")
-    L = TileLayout(24, 2, 1, ng=2, loopback=True)
+    ref = Engine(mk(), TileLayout(24, 2, 1, ng=ng), grid=g, dtype=dtype, device="cuda", backend="hip")
+    L = TileLayout(24, 2, 1, ng=ng, loopback=True)
     F = ref.physics.F
     e = Engine(mk(), L, grid=g, dtype=dtype, device="cuda", backend="hip", dt=ref.dt,
                transport=NativeBuffers(L.plan(0), F, dtype, torch.device("cuda")))

@@ -46,14 +46,14 @@ def test_single_gpu_solver_matches_cpu(limiter, tmp_path):
     assert type(g.runner).__name__ == "NativeStepper"
 
 
-def _spmd_worker(rank, world, port, t, outdir, comm, fused="auto", fail_xgmi=False):
+def _spmd_worker(rank, world, port, t, outdir, comm, fused="auto", fail_xgmi=False, limiter="mc"):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank), STSP_SHARE_GPU="1")
     if fail_xgmi:
         os.environ["STSP_FAIL_XGMI"] = "1"     # every ring setup raises: the chain lands on ipc
     import torch.distributed as dist
     try:
-        c = _cfg(world, t, out=os.path.join(outdir, "run"), comm="xgmi" if fail_xgmi else comm)
+        c = _cfg(world, t, out=os.path.join(outdir, "run"), comm="xgmi" if fail_xgmi else comm, limiter=limiter)
         c["runtime"]["fused"] = fused
         s = Solver(c, verbose=False)
         s.initialize()
@@ -62,7 +62,9 @@ def _spmd_worker(rank, world, port, t, outdir, comm, fused="auto", fail_xgmi=Fal
         # the default SPMD runtime is the fused step with the xGMI ring inside
         # it (every block of the rank's share resident); "off", or another
         # exchange: stage kernels (ipc: graph-replayed IPC copies)
-        assert (s.fused is not None) == (fused != "off" and comm == "xgmi" and not fail_xgmi), s.fused
+        # (the fused step refuses PPM: "auto" falls back to the stage kernels)
+        assert (s.fused is not None) == (fused != "off" and comm == "xgmi" and not fail_xgmi
+                                         and limiter != "ppm"), s.fused
         if comm == "ipc":
             assert s.runner.use_graph and s.runner.stats["graph_steps"] > 0, s.runner.stats
         s.save_checkpoint()
@@ -103,6 +105,27 @@ def test_spmd_xgmi_solver_matches_single_and_restarts(world, t, fused, comm, tmp
     b = np.load(os.path.join(out, "b.npy"))
     assert np.array_equal(a, r)      # same kernels, same order: bitwise
     assert np.array_equal(b, r)      # restart from step 6 re-delivers the remote ghosts
+
+
+@pytest.mark.parametrize("world,t", [(2, 1), (4, 2)])
+def test_spmd_xgmi_solver_ppm_takes_the_stage_kernels(world, t, tmp_path):
+    """PPM (three ghost layers) through the Solver with the default runtime:
+    the fused step refuses PPM, so ``fused: auto`` must fall back to the stage
+    kernels with the direct xGMI exchange (the worker asserts ``s.fused is None``
+    and ``s.comm == "xgmi"``), bitwise equal to one GPU with ``fused: off``,
+    restart from the step-6 checkpoint included."""
+    out = str(tmp_path)
+    mp.spawn(_spmd_worker, args=(world, _free_port(), t, out, "xgmi", "auto", False, "ppm"), nprocs=world, join=True)
+    c = _cfg(1, t, out=str(tmp_path / "ref"), limiter="ppm")
+    c["runtime"]["fused"] = "off"
+    ref = Solver(c, verbose=False)
+    ref.initialize()
+    ref.run(nsteps=10)
+    assert ref.fused is None
+    r = ref.gather_global()
+    assert np.isfinite(r).all()
+    assert np.array_equal(np.load(os.path.join(out, "a.npy")), r)
+    assert np.array_equal(np.load(os.path.join(out, "b.npy")), r)
 
 
 @pytest.mark.parametrize("fused", ["auto", "off"])

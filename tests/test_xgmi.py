@@ -123,7 +123,7 @@ def test_xgmi_loopback_march_matches_single(N, t, dtype):
     xg.close()
 
 
-def _worker(rank, world, port, N, t, steps, outdir, block=None, rounds=1):
+def _worker(rank, world, port, N, t, steps, outdir, block=None, rounds=1, limiter=None):
     import ctypes
     import torch.distributed as dist
     from stsphere.ops.native_runtime import NativeStepper
@@ -132,13 +132,15 @@ def _worker(rank, world, port, N, t, steps, outdir, block=None, rounds=1):
     torch.cuda.set_device(0)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        L = TileLayout(N, t, world, ng=2)
+        # limiter 4 (PPM): three ghost layers and 3 x 3 carried corners through the rings
+        mk = (lambda: ShallowWater("tc5")) if limiter is None else (lambda: ShallowWater("tc5", limiter=limiter))
+        L = TileLayout(N, t, world, ng=mk().halo)
         dev = torch.device("cuda:0")
         held = []
         for _ in range(rounds):
             # rounds > 1: the next exchange reuses this process's pooled ring
             # and the peers open its IPC handle again
-            e = Engine(ShallowWater("tc5"), L, rank, device=dev, backend="hip", dt=200.0, block=block,
+            e = Engine(mk(), L, rank, device=dev, backend="hip", dt=200.0, block=block,
                        transport=NativeBuffers(L.plan(rank), 4, torch.float64, dev))
             xg = XgmiHalo(e, timeout_s=5.0)
             ns = NativeStepper(e, use_graph=True, steps_per_graph=5, xgmi=xg)
