@@ -27,13 +27,18 @@ ARCH = os.environ.get("STSP_OFFLOAD_ARCH", "gfx950")
 # own-cell wave placement, nine waves, library sqrt, compare+select slopes,
 # march waves per SIMD) and the timing-only fused-step probe fp_alledge;
 # xgfence: system-scope fences around the fused step's xGMI ring (multi-rank
-# visibility diagnostic)
+# visibility diagnostic); hrt0: the fused step's hand-off as it was before
+# profiles/handoff_rt (tail cells on ring-owning threads, xg_wait polls, inner
+# faces on every wave), hrt1 / hrt12: its first / first two changes only
 VARIANT_FLAGS = {"": [], "diag": ["-DSTSP_STAMPS"],
                  "unfused": ["-DSTSP_FUSE_FACES=0"], "pe0": ["-DSTSP_PE_WAVE=0"],
                  "ownw0": ["-DSTSP_OWN_SKIP0=0"], "w9": ["-DSTSP_W10=0"], "swsqrt": ["-DSTSP_HW_SQRT=0"],
                  "selslope": ["-DSTSP_SIGN_SLOPE=0"], "wpe6": ["-DSTSP_WPE=6"], "wpe7": ["-DSTSP_WPE=7"],
                  "fp_alledge": ["-DSTSP_FPROBE_ALLEDGE=1"],
-                 "xgfence": ["-DSTSP_XG_FENCE=1"]}
+                 "xgfence": ["-DSTSP_XG_FENCE=1"],
+                 "hrt0": ["-DSTSP_FUSED_TAIL_OWN=0", "-DSTSP_FUSED_POLL2=0", "-DSTSP_FUSED_RF_MINB=1000"],
+                 "hrt1": ["-DSTSP_FUSED_POLL2=0", "-DSTSP_FUSED_RF_MINB=1000"],
+                 "hrt12": ["-DSTSP_FUSED_RF_MINB=1000"]}
 
 
 def lib_for(variant: str = "") -> str:

@@ -55,13 +55,34 @@
 #ifndef STSP_XG_FENCE
 #define STSP_XG_FENCE 0
 #endif
-// Tagged in-launch hand-off (FArgs::hx; the host picks it for blocks of at
-// most 8 cells, ops/fused.py::handoff_mode: faster at B = 6, slower at B = 16,
+// Tagged in-launch hand-off (FArgs::hx; the host's default at every block
+// size, one rank or several, ops/fused.py::handoff_mode: with fp64 cells packed
+// into 5 granules it is the faster form at B = 6 and at B = 16,
 // profiles/r6_handoff).  Its block-uniform branches cost the epoch path
 // nothing measurable (same box: 11.7-12.2 us/step with or without them);
 // STSP_FUSED_TAGH=0 compiles it out.
 #ifndef STSP_FUSED_TAGH
 #define STSP_FUSED_TAGH 1
+#endif
+// The hand-off's memory round trips (profiles/handoff_rt); the earlier forms
+// (0, 0 and an RF_MINB above every block size) are kept for A/B as the
+// library variants hrt0, hrt1 and hrt12 of ops/build.py:
+//   TAIL_OWN   tail cells on the threads that own a block cell (no ring cell),
+//              so no thread runs two waits in a row; 0: on threads [NU, NT)
+//   POLL2      fused_wait: after a failed poll the error word is loaded with
+//              the re-read of the granules (one round trip); 0: xg_wait
+//   RF_MINB    block sizes from which, in a waiting step of the tagged
+//              hand-off, the inner stage-1 faces go only to the threads that
+//              own a block cell and the ring waves poll at once; below it (a
+//              single wave would carry every inner pass) all threads share them
+#ifndef STSP_FUSED_TAIL_OWN
+#define STSP_FUSED_TAIL_OWN 1
+#endif
+#ifndef STSP_FUSED_POLL2
+#define STSP_FUSED_POLL2 1
+#endif
+#ifndef STSP_FUSED_RF_MINB
+#define STSP_FUSED_RF_MINB 12
 #endif
 
 namespace {
@@ -86,11 +107,17 @@ struct FD {
   // spilled 36-58 VGPRs, some of them reloaded inside the face loops (a
   // vmcnt wait per reload); the face work per SIMD is the same either way.
   // Each thread owns one window cell in owner order; the outer-ring cells
-  // beyond NT (loaded each step, never updated) are "tail" cells of threads
-  // [NU, NT).
+  // beyond NT (loaded each step, never updated) are "tail" cells.  They go to
+  // the threads that own a block cell, [0, B^2): in a waiting step of a
+  // multi-step launch those threads load nothing else, so no thread waits
+  // for two cells one after the other (TAIL_OWN = 0: to threads [NU, NT),
+  // which own a ring cell too).  tail_index() is the mapping.
   static constexpr int NU = H1 * H1;               // cells stage 1 updates
   static constexpr int NT = NU <= 768 ? 768 : 1024;
   static_assert(NU <= NT && W * W <= 2 * NT, "owner threads for every updated cell");
+  static constexpr int NTAIL = W * W > NT ? W * W - NT : 0;
+  static constexpr int NTO = STSP_FUSED_TAIL_OWN ? B * B : NT - NU;   // threads that carry tail cells
+  static constexpr int TPT = NTAIL ? (NTAIL + NTO - 1) / NTO : 1;     // tail cells per such thread
   static_assert(GMAX <= NT, "one fix-up thread per ghost entry");
   static_assert(2 * (B + 4 * (NS - 2)) * (B + 4 * (NS - 2) + 1) <= 32 * 64 && 2 * H1 * (H1 + 1) <= 32 * 64 + 64 * 64,
                 "face passes per stage fit the 32-entry pass table");
@@ -106,7 +133,7 @@ __device__ __forceinline__ int fregion(int X, int Y, int N) {
 
 // Cell t of the square annulus [lo, lo+L)^2 minus [lo+w, lo+L-w)^2: the w top
 // rows, the w bottom rows, then the side columns row by row.
-__device__ __forceinline__ void annulus(int t, int lo, int L, int w, int& u, int& v) {
+__host__ __device__ __forceinline__ constexpr void annulus(int t, int lo, int L, int w, int& u, int& v) {
   if (t < w * L) {
     u = lo + t % L; v = lo + t / L;
     return;
@@ -125,7 +152,7 @@ __device__ __forceinline__ void annulus(int t, int lo, int L, int w, int& u, int
 // Owner order: the block (square of stage NS), then the ring each earlier stage
 // adds, then the outer ring of width 2 (loaded, never updated).
 template <int NS, int B>
-__device__ __forceinline__ void owner_cell(int t, int& u, int& v) {
+__host__ __device__ __forceinline__ constexpr void owner_cell(int t, int& u, int& v) {
   using D = FD<NS, B>;
   constexpr int R = D::R;
   if (t < B * B) {
@@ -144,6 +171,43 @@ __device__ __forceinline__ void owner_cell(int t, int& u, int& v) {
     done += n;
   }
   u = -1; v = -1;
+}
+
+// Tail cell k of thread tid as an owner-order index (>= NT), or -1: FD's tail
+// mapping, the one place it is written down.
+template <int NS, int B>
+__host__ __device__ __forceinline__ constexpr int tail_index(int tid, int k) {
+  using D = FD<NS, B>;
+  if (!D::NTAIL || k >= D::TPT) return -1;
+  const int first = STSP_FUSED_TAIL_OWN ? 0 : D::NU;
+  if (tid < first || tid >= first + D::NTO) return -1;
+  const int idx = D::NT + (tid - first) + k * D::NTO;
+  return idx < D::W * D::W ? idx : -1;
+}
+
+// Owners and tails together hold every cell of the W x W window exactly once
+// (checked when the kernel is instantiated: the build is the test).
+template <int NS, int B>
+constexpr bool window_covered_once() {
+  using D = FD<NS, B>;
+  constexpr int W = D::W;
+  int cnt[W * W] = {};
+  for (int t = 0; t < D::NT; ++t) {
+    int idx[1 + D::TPT] = {};
+    idx[0] = t < W * W ? t : -1;
+    for (int k = 0; k < D::TPT; ++k) idx[1 + k] = tail_index<NS, B>(t, k);
+    for (int k = 0; k <= D::TPT; ++k) {
+      if (idx[k] < 0) continue;
+      if (k > 0 && idx[k] < D::NT) return false;
+      int u = -1, v = -1;
+      owner_cell<NS, B>(idx[k], u, v);
+      if (u < 0 || u >= W || v < 0 || v >= W) return false;
+      ++cnt[v * W + u];
+    }
+  }
+  for (int c = 0; c < W * W; ++c)
+    if (cnt[c] != 1) return false;
+  return true;
 }
 
 template <typename T>
@@ -218,9 +282,54 @@ __device__ __forceinline__ void fused_fail(int* err, unsigned code, int bid, int
   }
 }
 
+// The fused step's form of xg_wait (xg_ring.h; same bounds, same outcomes):
+// re-read the record's granules into g until every tag is `want`.  xg_spin
+// reads the error word in a load that depends on the failed poll, then sleeps
+// and polls again: three round trips in series for a poll that fails once.
+// Here the error word is loaded together with the re-read and both are tested
+// after one wait.  What has already arrived still costs no error-word traffic.
+template <class C, int SCOPE, bool FENCE = false, class Fail>
+__device__ __forceinline__ XgWait fused_wait(XgRec r, unsigned want, const int* err, long long timeout_ticks,
+                                             unsigned long long (&g)[C::W], Fail on_timeout) {
+#if STSP_FUSED_POLL2
+  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+  auto read = [&] {
+#pragma unroll
+    for (int k = 0; k < C::W; ++k) g[k] = __hip_atomic_load(r.p + k * r.stride, __ATOMIC_RELAXED, SCOPE);
+  };
+  auto arrived = [&] {
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < C::W; ++k) ok &= C::tag_ok(g[k], want);
+    return ok;
+  };
+  if (FENCE) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+  read();
+  if (arrived()) return XgWait::ok;
+  for (;;) {
+    if ((long long)(__builtin_amdgcn_s_memrealtime() - t0) > timeout_ticks) {
+      on_timeout();
+      return XgWait::timeout;
+    }
+    __builtin_amdgcn_s_sleep(1);
+    if (FENCE) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+    // (the error word after the granules: loads return in order, so the
+    // wait for it is the wait for the last granule; in front of them the
+    // compiler moved it to a scalar register behind a wait of its own)
+    read();
+    const unsigned e = __hip_atomic_load((gu32*)err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (arrived()) return XgWait::ok;
+    if (e != 0) return XgWait::aborted;
+  }
+#else
+  return xg_wait<C, SCOPE, FENCE>(r, want, err, timeout_ticks, g, on_timeout);
+#endif
+}
+
 // phase stamp (profiling): lane 0 of every wave, when a.stamps is set;
 // stamps[block][wave < 16][FST_W]: slots 0-15 clocks, 16 HW_ID (SIMD, CU, SE
-// of the wave), 17 XCC_ID (the XCD), 18 the dispatch-order blockIdx.x
+// of the wave), 17 XCC_ID (the XCD), 18 the dispatch-order blockIdx.x, 19 a
+// clock again (a waiting step's ring cells put, before the barrier)
 constexpr int FST_W = 32;
 #define FSTAMP(k)                                                                                \
   do {                                                                                           \
@@ -306,7 +415,9 @@ template <typename T, int LIM, int NS, int B, bool XG, bool MULTI>
 __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a) {
   using D = FD<NS, B>;
   constexpr int W = D::W, WS = D::WS, WW = D::WW, GB = D::GB, R = D::R, L1 = D::L1, H1 = D::H1;
-  constexpr int NFX = D::NFX, NFL = D::NFL, NT = D::NT, NU = D::NU;
+  constexpr int NFX = D::NFX, NFL = D::NFL, NT = D::NT;
+  static_assert(window_covered_once<NS, B>(), "owner and tail cells cover the window exactly once");
+  constexpr bool RING_FIRST = B >= STSP_FUSED_RF_MINB;   // see STSP_FUSED_RF_MINB
   // PFN: panel-edge blocks take each face's normal from a per-face table
   // (FArgs::nrmf, host-built from the region tables) and learn from the host
   // which face passes hold a face next to a panel-edge line; the other passes
@@ -487,7 +598,7 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
       // until every tag carries this step; a timeout sets err and falls through
       unsigned long long gr[HX<T>::W];
       const XgRec r = ring_slot_record<HX<T>>(a.recv, a.ring, xg_in_slot(xe_), -2 - src);
-      xg_wait<HX<T>, XG_RING_SCOPE, STSP_XG_FENCE != 0>(r, xg_in_tag(xe_), a.err, a.timeout_ticks, gr, [&] {
+      fused_wait<HX<T>, XG_RING_SCOPE, STSP_XG_FENCE != 0>(r, xg_in_tag(xe_), a.err, a.timeout_ticks, gr, [&] {
         fused_fail(a.err, 1u, bid, xe_, -2 - src, (int)HX<T>::tag_of(gr[0]));
       });
       HX<T>::unpack(gr, Q);
@@ -509,16 +620,60 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
   };
   // a window cell of another block at step xe_ > launch start, tagged hand-off
   auto load_tagged = [&](int src_, T (&q)[4], int xe_) {
+#if STSP_FUSED_TAIL_OWN
+    // per step, like load_state_of: a record address kept in registers across
+    // the steps was spilled and reloaded in front of the poll
+    asm volatile("" : "+v"(src_));
+#endif
     unsigned long long gr[HX<T>::W];
     const XgRec r = hx_record((unsigned)src_, xe_ & 1);
-    xg_wait<HX<T>, XG_LOCAL_SCOPE>(r, xg_in_tag(xe_), a.err, a.timeout_ticks, gr, [&] {
+    fused_wait<HX<T>, XG_LOCAL_SCOPE>(r, xg_in_tag(xe_), a.err, a.timeout_ticks, gr, [&] {
       fused_fail(a.err, 2u, bid, xe_, src_, (int)HX<T>::tag_of(gr[0]));
     });
     HX<T>::unpack(gr, q);
   };
   auto load_state = [&](const T* Qin, int xe_) { load_state_of(src, Q, Qin, xe_); };
+  // tail cells (outer ring beyond NT, see FD), loaded and put every step:
+  // their window index and source are static, so they are resolved once.  A
+  // step issues the tail loads with the ring loads; the first step's go out
+  // here, with the other global loads of the prologue
+  constexpr int TPT = D::TPT;
+  int tl_wi[TPT], tl_src[TPT], tl_ci[TPT];
+  unsigned long long tl_cd[TPT];
+#pragma unroll
+  for (int k = 0; k < TPT; ++k) {
+    const int idx = tail_index<NS, B>(tid, k);
+    tl_wi[k] = -1;
+    tl_src[k] = -1;
+    tl_ci[k] = 0;
+    tl_cd[k] = 0;
+    if (idx >= 0) {
+      int tu, tv, g_, I_, J_;
+      owner_cell<NS, B>(idx, tu, tv);
+      tl_src[k] = cell_src(tu, tv, g_, I_, J_);
+      tl_wi[k] = tv * WS + tu;
+      tl_ci[k] = tv * (W + 1) + tu;
+      if (edge) tl_cd[k] = a.code[(long)bid * W * W + tv * W + tu];
+    }
+  }
+  auto tail_load = [&](const T* Qin, int xe_, T (&tq)[TPT][4]) {
+#pragma unroll
+    for (int k = 0; k < TPT; ++k)
+      if (tl_wi[k] >= 0) load_state_of(tl_src[k], tq[k], Qin, xe_);
+  };
+  auto tail_load_tagged = [&](int xe_, T (&tq)[TPT][4]) {
+#pragma unroll
+    for (int k = 0; k < TPT; ++k) {
+      if (tl_wi[k] >= 0) {
+        if (tl_src[k] >= 0) load_tagged(tl_src[k], tq[k], xe_);
+        else load_state_of(tl_src[k], tq[k], nullptr, xe_);   // another rank's cell (ring) or none
+      }
+    }
+  };
   T* const buf[2] = {const_cast<T*>(a.Q), a.out};
   load_state(buf[0], xe);
+  T tq0[TPT][4];
+  tail_load(buf[0], xe, tq0);
   if (loaded && in1) {
     using V2 = typename V16<T>::type;
     const T* cp = a.crec + (long)(cJ * N + cI) * 8;
@@ -593,45 +748,19 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
     p[4 * WW] = tsqrt(a.g * tmax(q[0], T(0)));
   };
   auto put = [&](const T (&q)[4]) { put_at(wi, q); };
-  // tail cells (outer ring beyond NT, see FD), loaded and put every step:
-  // their window index and source are static, so they are resolved once and a
-  // step issues the tail loads together with the ring loads (one memory round
-  // trip for the threads that own both, not two in a row)
-  constexpr int NTAIL = W * W > NT ? W * W - NT : 0;
-  constexpr int TPT = NTAIL ? (NTAIL + (NT - NU) - 1) / (NT - NU) : 1;
-  int tl_wi[TPT], tl_src[TPT];
-#pragma unroll
-  for (int k = 0; k < TPT; ++k) {
-    const int idx = NT + (tid - NU) + k * (NT - NU);
-    tl_wi[k] = -1;
-    tl_src[k] = -1;
-    if (NTAIL && tid >= NU && idx < W * W) {
-      int tu, tv, g_, I_, J_;
-      owner_cell<NS, B>(idx, tu, tv);
-      tl_src[k] = cell_src(tu, tv, g_, I_, J_);
-      tl_wi[k] = tv * WS + tu;
-      if (edge) s_code[tv * CS + tu] = a.code[(long)bid * W * W + tv * W + tu];
-    }
-  }
-  auto tail_load = [&](const T* Qin, int xe_, T (&tq)[TPT][4]) {
-#pragma unroll
-    for (int k = 0; k < TPT; ++k)
-      if (tl_wi[k] >= 0) load_state_of(tl_src[k], tq[k], Qin, xe_);
-  };
-  auto tail_load_tagged = [&](int xe_, T (&tq)[TPT][4]) {
-#pragma unroll
-    for (int k = 0; k < TPT; ++k) {
-      if (tl_wi[k] >= 0) {
-        if (tl_src[k] >= 0) load_tagged(tl_src[k], tq[k], xe_);
-        else load_state_of(tl_src[k], tq[k], nullptr, xe_);   // another rank's cell (ring) or none
-      }
-    }
-  };
   auto tail_put = [&](const T (&tq)[TPT][4]) {
 #pragma unroll
     for (int k = 0; k < TPT; ++k)
       if (tl_wi[k] >= 0) put_at(tl_wi[k], tq[k]);
   };
+  // the first step's tail cells (nothing reads the window before the barrier
+  // at the loop top)
+  tail_put(tq0);
+  if (edge) {
+#pragma unroll
+    for (int k = 0; k < TPT; ++k)
+      if (tl_wi[k] >= 0) s_code[tl_ci[k]] = tl_cd[k];
+  }
   // panel-edge lines in the window (block-uniform): x-lines X = 0 (W) / X = N
   // (E), y-lines Y = 0 (S) / Y = N (N); far away when absent
   const int kx0 = (flags & 2) ? -X0 : -1000, kx1 = (flags & 4) ? N - X0 : -1000;
@@ -766,10 +895,7 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
   if (wait) {
     if (tid < B * B) enter_cell();
   } else {
-    T tq[TPT][4];
-    tail_load(buf[0], xe, tq);
-    tail_put(tq);
-    enter_cell();
+    enter_cell();          // (its tail cells went in with the prologue)
   }
   __syncthreads();
   if (wait && !tagh && !pcell && tid < 64) {
@@ -790,10 +916,18 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
                                                                     __HIP_MEMORY_SCOPE_AGENT));
     });
   } else {
-    // ... while the other waves compute the inner stage-1 faces (tagged
-    // hand-off: every wave; the ring loads below are the wait)
+    // ... while the other waves compute the inner stage-1 faces.  The ring
+    // loads below are the tagged hand-off's wait: there (RING_FIRST) the
+    // faces go to the threads that own a block cell, which load at most a
+    // tail cell, and the ring waves go from the barrier straight to their
+    // polls, in flight while the faces run
     const bool w0 = wait && !tagh && !pcell;
-    const int t0 = w0 ? tid - 64 : tid, dt_ = w0 ? NT - 64 : NT;
+    // (from the last of those threads down, so the first threads, which then
+    // wait for a tail cell, run one round; at B = 16 their wave still ends
+    // last, with the ring waves: it waits for the producer, not for the faces)
+    const bool rf = RING_FIRST && wait && tagh;
+    const int t0 = w0 ? tid - 64 : (rf ? (tid < B * B ? B * B - 1 - tid : NI) : tid);
+    const int dt_ = w0 ? NT - 64 : (rf ? B * B : NT);
     for (int t = t0; t < NI; t += dt_) inner_face(t);
   }
   FSTAMP(1);
@@ -838,6 +972,7 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
       }
     }
     tail_put(tq);
+    FSTAMP(19);              // this wave's ring and tail cells are in the window (before the barrier)
     __syncthreads();
   }
   FSTAMP(2);

@@ -172,9 +172,19 @@ def main():
         torch.cuda.synchronize()
         md.stamps = 0
         fk.check()
-        v2 = st.cpu().numpy()[:, :, :16].astype(np.float64).reshape(nb, nw, 16)
+        raw2 = st.cpu().numpy()
+        v2 = raw2[:, :, :16].astype(np.float64).reshape(nb, nw, 16)
         v2 = np.where(v2 == 0, np.nan, v2)
         top = np.nanmin(v2[:, :, 13], 1)
+        # per-wave ring arrival (slot 19: the wave's ring and tail cells are in
+        # the window, before the barrier), from the block's loop top, mean over
+        # each block class: which wave the hand-off's barrier waits for
+        ring = raw2[:, :, 19].astype(np.float64)
+        ring = np.where(ring == 0, np.nan, ring) - top[:, None]
+        with np.errstate(all="ignore"):
+            out["multi_wave_ring_cycles"] = {
+                c_: [None if np.isnan(x) else int(x) for x in np.nanmean(ring[m_], 0)] if m_.any() else None
+                for c_, m_ in (("int", ~edge), ("edge", side), ("corner", corner))}
         rel2 = np.nanmax(v2 - top[:, None, None], 1)
         idx = [13, 1, 2, 3, 4, 5, 6, 7, 8, 9]
         nm2 = ["loop_top", "wait_load_put", "bar"] + sum([[f"s{s}_faces", f"s{s}_upd"] for s in range(1, 4)], []) + ["end"]
