@@ -304,9 +304,9 @@ def second_difference(n: int, h: float, bc: str = "dirichlet", dtype=torch.float
     D[i, i] = -2.0
     D[i[:-1], i[:-1] + 1] = 1.0
     D[i[1:], i[1:] - 1] = 1.0
-    if bc == "periodic":
-        D[0, n - 1] = 1.0
-        D[n - 1, 0] = 1.0
+    if bc == "periodic":       # added, not assigned: at n = 2 both neighbours are the other row, at n = 1 the row itself
+        D[0, n - 1] += 1.0
+        D[n - 1, 0] += 1.0
     return D / (h * h)
 
 
@@ -369,14 +369,37 @@ class LowRankDiffusion:
             A, B = torch.cat([A, c * (self.D @ A)], dim=1), torch.cat([B + c * (self.D @ B), B], dim=1)
         return recompress(A, B, self.eps, self.max_rank)
 
+    def _persistent_check(self, N: int, r: int, max_rank: int):
+        """(code, cap) of the native admission rule (stsp_tt_persist_check,
+        host only): 0 accepted, -1 arguments, -2 the factor does not fit,
+        -3 max_rank above the cap."""
+        import ctypes
+        from ..ops import native
+        cap = ctypes.c_int(0)
+        rc = native.require_native().stsp_tt_persist_check(int(N), int(r), int(self.substeps), int(max_rank),
+                                                           ctypes.byref(cap))
+        return int(rc), int(cap.value)
+
+    def persistent_rank_cap(self, N: int) -> int:
+        """Largest rank ``run_persistent`` can hold at N rows with this
+        solver's substeps (0: N itself is out of range): the next step expands
+        a rank-r factor to N x (r << substeps) doubles in LDS."""
+        return self._persistent_check(N, 1, 0)[1]
+
     def run_persistent(self, U: LowRankField, dt: float, ncalls: int,
                        stamps: Optional[torch.Tensor] = None) -> LowRankField:
         """``ncalls`` factored steps (each ``substeps`` explicit substeps and
         one CholeskyQR3 recompression, the numerics of ``qr="cholqr3n"``) in
         ONE launch of the persistent kernel (ops/csrc/tt_persist.hip): two
         workgroups keep the factors in LDS across the steps and hand the k x k
-        core between them on the device.  fp64, N <= 1024, 2^substeps r <= 16,
-        N k <= 12288.  The new rank is read once, after the launch.
+        core between them on the device.  fp64, 4 <= N <= 1024.  The rank
+        may grow inside the launch, so the kernel caps it at
+        ``persistent_rank_cap(N)`` = min(16 >> substeps, (12288 // N) >>
+        substeps): the largest rank whose next expansion (2^substeps times as
+        many columns) still fits the 16-column core arrays and the 12288-double
+        LDS factor.  The starting rank and an explicit ``max_rank`` must not
+        exceed that cap (RuntimeError, before any launch); ``max_rank=None``
+        means the cap.  The new rank is read once, after the launch.
         ``stamps``: optional int64 [ncalls, 2, 16] device tensor of per-phase
         shader clocks (expand, three QR passes, core hand-offs, product)."""
         from ..ops import native
@@ -385,6 +408,13 @@ class LowRankDiffusion:
         ns = self.substeps
         if U.A.dtype != torch.float64 or U.A.device.type != "cuda":
             raise ValueError("persistent factored step: fp64 CUDA factors")
+        if int(ncalls) < 1:
+            raise ValueError("persistent factored step: ncalls >= 1")
+        rc, cap = self._persistent_check(N, r, self.max_rank or 0)
+        if rc != 0:
+            raise RuntimeError(f"persistent factored step refused ({rc}): N = {N}, rank {r}, max_rank "
+                               f"{self.max_rank}, {ns} substeps; the rank cap of this shape is {cap} "
+                               f"(min(16 >> substeps, (12288 // N) >> substeps), 4 <= N <= 1024)")
         A = U.A if U.A.stride(1) == 1 else U.A.contiguous()
         B = U.B if U.B.stride(1) == 1 else U.B.contiguous()
         dev = A.device

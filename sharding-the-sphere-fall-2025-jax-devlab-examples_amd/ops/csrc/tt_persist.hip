@@ -8,7 +8,8 @@
 // two products) plus a 4-byte read-back of the new rank: at N = 1024 every
 // kernel is 1.5-8 us of mostly idle GPU (profiles/r4_tt/tt_step_trace_N1024_r3.txt).
 // Here workgroup s (s = 0: the row factor A, s = 1: the column factor B) keeps
-// its N x k factor in LDS for the whole launch (N k <= 12288 doubles, 96 KiB)
+// its N x k factor in LDS for the whole launch (N k <= 12288 doubles, 96 KiB;
+// stsp_tt_persist_check caps the in-launch rank so every expansion fits)
 // and runs, per step:
 //
 //   expand    nsub explicit substeps on the factors, [A, c D A] [B + c D B, B]
@@ -483,6 +484,25 @@ int stsp_tt_persist_limits(int* nk_max, int* k_max) {
   return 0;
 }
 
+// Admission rule of the persistent step (host only, no HIP call).  A launch
+// may let the rank reach cap = min(TP_KP >> nsub, (TP_NK / N) >> nsub): the
+// largest rank whose NEXT expansion (rank << nsub columns) still fits the
+// kernel's k x k arrays and its N x k LDS factor.  Returns 0 and the cap in
+// cap_out (null allowed), -1 for arguments out of range, -2 for a factor the
+// kernel cannot hold (N > 1024, or a starting rank above the cap) and -3 for
+// an explicit max_rank above the cap; max_rank <= 0 means the cap.
+int stsp_tt_persist_check(int N, int r, int nsub, int max_rank, int* cap_out) {
+  if (cap_out) *cap_out = 0;
+  if (N < 4 || r < 1 || nsub < 0 || nsub > 30) return -1;
+  if (N > TP_T * TP_RPT) return -2;
+  const int kp = TP_KP >> nsub, kn = (TP_NK / N) >> nsub;
+  const int cap = kp < kn ? kp : kn;
+  if (cap_out) *cap_out = cap;
+  if (r > cap) return -2;
+  if (max_rank > cap) return -3;
+  return 0;
+}
+
 // ncalls factored diffusion steps (each: nsub explicit substeps + one
 // CholeskyQR3 recompression) of U = A B^T in one launch.  fp64.  xch: 512
 // doubles, flags: 4 unsigned (zeroed here, before the launch).  The final
@@ -491,11 +511,11 @@ int stsp_tt_persist(const double* A, int lda, const double* B, int ldb, int N, i
                     double ih2, int periodic, double eps, int max_rank, double* xch, unsigned* flags, double* outA,
                     double* outB, int ldo, int* rn_out, unsigned long long* stamps, double timeout_s,
                     hipStream_t st) {
-  if (N < 4 || r < 1 || nsub < 0 || ncalls < 1) return -1;
-  const int k = r << nsub;
-  if (k > TP_KP || (long)N * k > TP_NK || N > TP_T * TP_RPT) return -2;
-  if (max_rank > 0 && (max_rank << nsub) > TP_KP) return -3;
-  if (max_rank <= 0) max_rank = TP_KP >> nsub;     // the next step's expansion must fit too
+  int cap = 0;
+  const int adm = stsp_tt_persist_check(N, r, nsub, max_rank, &cap);
+  if (adm != 0) return adm;
+  if (ncalls < 1) return -1;
+  if (max_rank <= 0) max_rank = cap;     // every later step's expansion must fit X and the k x k arrays
   TPArgs a;
   a.A = A; a.B = B; a.lda = lda; a.ldb = ldb; a.N = N; a.r0 = r; a.ncalls = ncalls; a.nsub = nsub;
   a.periodic = periodic; a.max_rank = max_rank; a.c = c; a.ih2 = ih2; a.eps = eps;

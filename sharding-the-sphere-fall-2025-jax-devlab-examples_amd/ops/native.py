@@ -248,6 +248,9 @@ def _declare_tt(L):
     L.stsp_tt_persist.restype = ci
     L.stsp_tt_persist_limits.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci)]
     L.stsp_tt_persist_limits.restype = ci
+    # host-only admission rule of the persistent step: (N, r, nsub, max_rank, cap_out)
+    L.stsp_tt_persist_check.argtypes = [ci, ci, ci, ci, ctypes.POINTER(ci)]
+    L.stsp_tt_persist_check.restype = ci
 
 
 def available() -> bool:

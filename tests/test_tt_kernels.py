@@ -371,14 +371,31 @@ def test_persistent_factored_step_matches_native_chain(N, substeps, ncalls, bc):
     assert float((G - U).norm() / U.norm()) < 1e-9
 
 
+@pytest.fixture
+def core_mode(request):
+    """The core mode of stsp_tt_recompress / stsp_tt_lr_step3 is a
+    process-global (stsp_tt_set_core; a LowRankDiffusion step sets it and
+    leaves it): set it to request.param ("device": tt_core_kernel for
+    k <= 32, or "host") for one test and restore the old value."""
+    from stsphere.ops import native
+    L = native.require_native()
+    old = L.stsp_tt_set_core(1 if request.param == "device" else 0)
+    try:
+        yield request.param
+    finally:
+        L.stsp_tt_set_core(old)
+
+
 @pytest.mark.gpu
+@pytest.mark.parametrize("core_mode", ["device", "host"], indirect=True)
 @pytest.mark.parametrize("NA,NB,k,r", [(300, 301, 8, 5), (1024, 1025, 24, 12), (500, 480, 40, 30), (2000, 2001, 64, 20),
                                        (64, 65, 64, 64)])
-def test_native_recompress_matches_qr_svd(NA, NB, k, r):
+def test_native_recompress_matches_qr_svd(NA, NB, k, r, core_mode):
     """stsp_tt_recompress (one native call: CholeskyQR3 of both factors, the
     k x k core on the device or the host, two MFMA products) against the
     Householder QR + SVD rounding of the same product: same rank, product to
-    1e-12; rank-deficient inputs (k columns, rank r) are rounded to r."""
+    1e-12; rank-deficient inputs (k columns, rank r) are rounded to r.  Both
+    core modes, set here and not inherited from whichever test ran before."""
     from stsphere.ops import tt_ops
     g = torch.Generator().manual_seed(NA + k)
     X = torch.randn(NA, r, generator=g, dtype=torch.float64)
