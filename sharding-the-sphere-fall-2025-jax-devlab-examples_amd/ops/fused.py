@@ -39,6 +39,7 @@ Stage ``s`` (1-based) updates the square ``[lo_s, hi_s)`` with
 """
 from __future__ import annotations
 
+import hashlib
 import os
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
@@ -1456,9 +1457,17 @@ def global_cell_records(engine) -> np.ndarray:
     """[6 N N, 12] cell records of every cell of the grid, indexed by global
     flat id: 1/A, centre (3), grad b (3), the curvature sum S = sum(L m) over
     the cell's four faces with outward normals (3; the kernel's curvature
-    balance is g h^2 / 2 * S / A, models/swe.py), 0, 0."""
+    balance is g h^2 / 2 * S / A, models/swe.py), 0, 0.
+
+    Cached on the grid per topography: the key holds a digest of the physics'
+    b array, so two physics that differ only in b never share records."""
     e = engine
-    key = ("global_rec12", e.layout.N, e.physics.name, getattr(e.physics, "case", None))
+    gf = getattr(e.physics, "global_fields", None)
+    b_digest = None
+    if gf is not None:
+        b = np.ascontiguousarray(gf(e.grid)[2], dtype=np.float64)
+        b_digest = hashlib.sha1(b.tobytes()).hexdigest()
+    key = ("global_rec12", e.layout.N, e.physics.name, b_digest)
     cache = getattr(e.grid, "_cache", {})
     if key in cache:
         return cache[key]

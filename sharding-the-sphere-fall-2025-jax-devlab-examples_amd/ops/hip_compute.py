@@ -272,6 +272,16 @@ class HipCompute:
         cg = os.environ.get("STSP_MARCH_COMPACT", "1" if e.dtype == torch.float64 else "0") != "0"
         self.mt = march_tables(e) if self.march and cg else None
 
+    @property
+    def march_geometry(self) -> Optional[str]:
+        """Geometry path of the streaming stage as the launches select it (the
+        kernel runs compact exactly when the descriptor carries the tables of
+        ``march_tables``): "compact", "records" (per-tile cell records), or
+        None when the engine runs the block kernel."""
+        if not self.march:
+            return None
+        return "compact" if self.mt is not None else "records"
+
     def use_march_with_xgmi(self) -> bool:
         """Switch a rank with remote ghosts to the streaming stage when the size
         rule wants it: the direct xGMI exchange (XgmiHalo) delivers its remote

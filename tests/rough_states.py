@@ -15,6 +15,9 @@ every primitive field into every arm:
 ``scalar``    (advection, diffusion) max|q0| U(0, 1) with 30 % of the cells
               exactly 0.
 
+``TopographySWE`` puts a topography with a non-zero gradient under every cell
+(the tc5 cone covers 3 % of them), for the tests of the term -g h grad b.
+
 Every state is a function of the global grid alone (seeded
 ``torch.Generator``), so engines of any layout, rank count and precision get
 the same field: build it once with ``global_state`` and ``install`` it.
@@ -27,6 +30,7 @@ import torch
 from stsphere.engine import assemble_global
 from stsphere.models.base import PPM, cells_x, cells_y, extend
 from stsphere.models.geometry import CubedSphereGrid
+from stsphere.models.swe import ShallowWater
 
 SWE_CLASSES = ("rough", "plateau", "zero_mom")
 PATCH = (2, 3)            # plateau patch: 2 cells along x, 3 along y
@@ -108,6 +112,55 @@ def make_state(engines, cls: str, seed: int = 0) -> torch.Tensor:
 @functools.lru_cache(maxsize=None)
 def grid_of(N: int) -> CubedSphereGrid:
     return CubedSphereGrid(N)
+
+
+# ---------------------------------------------------------------------------
+# topography in every cell
+# ---------------------------------------------------------------------------
+
+def topography(grid: CubedSphereGrid) -> np.ndarray:
+    """b [6, N, N] in metres, non-zero with a non-zero gradient in every cell:
+    300 (1.5 + x y + 0.7 z x - 0.5 y z + 0.4 x) + 100 u with (x, y, z) the cell
+    centre and u ~ U(-1, 1) per cell (56 m <= b <= 785 m at C24).  The smooth
+    part has no symmetry of the cube; the noise makes every one-cell shift or
+    reversal of a ghost strip visible."""
+    p = np.asarray(grid.centers(), dtype=np.float64)
+    x, y, z = p[..., 0], p[..., 1], p[..., 2]
+    gen = torch.Generator().manual_seed(3000)
+    u = _uniform(gen, p.shape[:-1], -1.0, 1.0).numpy()
+    return 300.0 * (1.5 + x * y + 0.7 * z * x - 0.5 * y * z + 0.4 * x) + 100.0 * u
+
+
+class TopographySWE(ShallowWater):
+    """A shallow-water case (depth and wind of the base case) over
+    ``topography``: the tc5 cone covers 3 % of the cells, two panels and one
+    cube edge, so every rendering of -g h grad b is otherwise untested
+    almost everywhere.  Only ``global_fields`` differs: setup, the streaming
+    stage's b table and the fused step's records read b through it."""
+
+    def global_fields(self, grid: CubedSphereGrid):
+        h, wind, _ = super().global_fields(grid)
+        return h, wind, topography(grid)
+
+
+SIDE_STRIP = {0: (slice(1, -1), 0), 1: (slice(1, -1), -1), 2: (0, slice(1, -1)), 3: (-1, slice(1, -1))}   # W E S N
+
+
+def gradb_with_reversed_ghost_strip(geo, b: np.ndarray, tile: int, side: int) -> np.ndarray:
+    """grad b [3, T, n, n] (the layout of ``Engine.tens["gradb"]``) of the rank
+    geometry ``geo`` with the layer-0 ghost strip of b on ``side`` (0 W, 1 E,
+    2 S, 3 N) of local tile ``tile`` read in reversed order: the mistake a
+    wrong orientation on a reversed cube edge makes.  ``geo`` is left as it
+    was."""
+    keep = geo.ext1
+    try:
+        geo.ext1 = keep.copy()
+        strip = geo.ext1[tile][SIDE_STRIP[side]]
+        geo.ext1[tile][SIDE_STRIP[side]] = strip[::-1].copy()
+        gb = geo.fv_gradient(b)
+    finally:
+        geo.ext1 = keep
+    return np.moveaxis(gb, -1, 0)
 
 
 # ---------------------------------------------------------------------------

@@ -13,7 +13,7 @@ import functools
 import pytest
 import torch
 
-from rough_states import global_of, grid_of, increment_error, install, make_state
+from rough_states import TopographySWE, global_of, grid_of, increment_error, install, make_state
 from stsphere.engine import Engine, VirtualCluster
 from stsphere.models.advection import Advection
 from stsphere.models.diffusion import Diffusion
@@ -31,6 +31,8 @@ def _physics(kind, lim):
         return Advection(limiter=lim)
     if kind == "diff":
         return Diffusion()
+    if kind == "topo":                  # tc5 over topography in every cell (tests/test_topography_kernels.py)
+        return TopographySWE("tc5", limiter=lim)
     return ShallowWater(kind, limiter=lim)
 
 
