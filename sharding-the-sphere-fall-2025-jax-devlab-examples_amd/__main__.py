@@ -8,10 +8,15 @@
     schedule                                           print the reference 4-stage halo schedule
     roofline                                           slide-19 roofline / TT model for MI355X
     plot HISTORY.zarr FIELD OUTDIR [--log] [--products frames,band,six] [--every K] [--latlon NLAT NLON]
+                                    [--spectrum LMAX]
                                                        sphere frames, equatorial band, six-panel;
-                                                       --latlon: regridded image + zonal-mean profile
+                                                       --latlon: regridded image + zonal-mean profile;
+                                                       --spectrum: log-log power per degree, first and last frame
     regrid HISTORY.zarr FIELD NLAT NLON OUT.npz        regrid a history field (or u, v of a shallow-water
                                                        history) to the cell-centred lat-lon grid, on the CPU
+    spectrum HISTORY.zarr FIELD LMAX OUT.npz           power per degree 0 .. LMAX of a history field (``ke``:
+                                                       the kinetic-energy spectrum of a shallow-water
+                                                       history), on the CPU
     ensemble CONFIG.yaml [--members M] [--amplitude A] [--days D | --nsteps K]
                                                        perturbed members of one config on one device
     build                                              compile the gfx950 library
@@ -48,12 +53,19 @@ def main(argv=None):
     p.add_argument("--every", type=int, default=1)
     p.add_argument("--latlon", type=int, nargs=2, metavar=("NLAT", "NLON"), default=None,
                    help="also write the last frame regridded to NLAT x NLON with its zonal-mean profile")
+    p.add_argument("--spectrum", type=int, metavar="LMAX", default=None,
+                   help="also write the log-log power per degree 0 .. LMAX of the first and the last frame")
     rg = sub.add_parser("regrid")
     rg.add_argument("history")
     rg.add_argument("field")
     rg.add_argument("nlat", type=int)
     rg.add_argument("nlon", type=int)
     rg.add_argument("out")
+    sp = sub.add_parser("spectrum")
+    sp.add_argument("history")
+    sp.add_argument("field")
+    sp.add_argument("lmax", type=int)
+    sp.add_argument("out")
     en = sub.add_parser("ensemble")
     en.add_argument("config")
     en.add_argument("--members", type=int, default=2)
@@ -88,6 +100,21 @@ def main(argv=None):
             os.makedirs(a.outdir, exist_ok=True)
             print(latlon_image(r["field"][-1], r["lat"], r["lon"], os.path.join(a.outdir, f"{a.field}_latlon.png"),
                                title=f"{a.field}, day {r['time'][-1] / 86400.0:.2f}", zonal=r["zonal_mean"][-1]))
+        if a.spectrum is not None:
+            from .utils.viz import spectrum_plot
+            r = spectrum_history(a.history, a.field, a.spectrum)
+            os.makedirs(a.outdir, exist_ok=True)
+            k = [0, len(r["time"]) - 1] if len(r["time"]) > 1 else [0]
+            print(spectrum_plot(r["spectrum"][k], os.path.join(a.outdir, f"{a.field}_spectrum.png"),
+                                title=f"{a.field}: power per degree",
+                                ylabel="E_l (m^2 / s^2)" if a.field == "ke" else "power per degree",
+                                labels=[f"day {r['time'][j] / 86400.0:.2f}" for j in k]))
+        return 0
+    if a.cmd == "spectrum":
+        import numpy as np
+        r = spectrum_history(a.history, a.field, a.lmax)
+        np.savez(a.out, **r)
+        print(json.dumps({"out": a.out, "field": a.field, "shape": list(r["spectrum"].shape)}))
         return 0
     if a.cmd == "regrid":
         import numpy as np
@@ -177,6 +204,49 @@ def regrid_history(history: str, field: str, nlat: int, nlon: int) -> dict:
         out.append(ml.winds(fr[0], fr[1:4], tb)[("u", "v").index(field)] if wind else ml.regrid(fr, tb)[0])
     out = torch.stack(out)
     return {"field": out.numpy(), "zonal_mean": ml.zonal_mean(out).numpy(), "lat": lat, "lon": lon,
+            "time": zarr_lite.read_array(history, "time")}
+
+
+def spectrum_history(history: str, field: str, lmax: int) -> dict:
+    """Power per degree of every frame of a history field with the PyTorch
+    twin on the CPU (models/spectra.py): spectrum [frames, L+1], degree, time.
+    ``ke``: the kinetic-energy spectrum from the h, mx, my, mz of a
+    shallow-water history (vorticity and divergence by the derived-field twin)."""
+    import numpy as np
+    import torch
+    from .models import spectra as ms
+    from .models.geometry import EARTH_RADIUS, CubedSphereGrid
+    from .utils import zarr_lite
+    have = zarr_lite.list_arrays(history)
+    if field in ("u", "v") and field not in have:
+        raise ValueError(f"{field!r} is a vector component, not a scalar on the sphere; use the field 'ke' for the "
+                         f"kinetic-energy spectrum of the winds")
+    ke = field == "ke" and field not in have
+    need = ["h", "mx", "my", "mz"] if ke else [field]
+    missing = [f for f in need if f not in have]
+    if missing:
+        raise ValueError(f"{history}: no array {missing} (it holds {[f for f in have if f not in ('time', 'step')]})")
+    src = np.stack([zarr_lite.read_array(history, f) for f in need], 1)       # [frames, C, 6, N, N]
+    N = src.shape[-1]
+    cfg = (zarr_lite.read_attrs(history).get("config") or {})
+    radius = (cfg.get("grid") or {}).get("radius") or EARTH_RADIUS
+    grid = CubedSphereGrid(N, radius)
+    out = []
+    if ke:
+        from .engine import Engine
+        from .models.swe import ShallowWater
+        from .parallel.layout import TileLayout
+        e = Engine(ShallowWater((cfg.get("physics") or {}).get("case") or "tc5"), TileLayout(N, 1, 1, ng=2), grid=grid)
+        sp = e.spectra(lmax)
+        for fr in torch.as_tensor(np.ascontiguousarray(src, dtype=np.float64)):
+            e.set_state(fr)
+            c = sp.partial_tiles(e.derived()[0][:2])
+            out.append(ms.ke_spectrum(c[0], c[1], radius))
+    else:
+        tb = ms.grid_tables(grid, lmax)
+        for fr in torch.as_tensor(np.ascontiguousarray(src, dtype=np.float64)):
+            out.append(ms.power(ms.analyse(fr.reshape(1, -1), tb))[0])
+    return {"spectrum": torch.stack(out).numpy(), "degree": np.arange(lmax + 1),
             "time": zarr_lite.read_array(history, "time")}
 
 

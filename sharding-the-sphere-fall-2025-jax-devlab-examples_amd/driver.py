@@ -36,13 +36,14 @@ from .models.base import limiter_code
 from .models.derived import FIELDS as DERIVED_FIELDS, INVARIANTS
 from .models.diffusion import Diffusion
 from .models.geometry import DAY, EARTH_RADIUS, CubedSphereGrid
+from .models.spectra import check_lmax, ke_spectrum as spectra_ke, power as spectra_power
 from .models.swe import ShallowWater
 from .parallel.comm import NativeBuffers, TorchDistTransport
 from .parallel.layout import TileLayout
 from .parallel.mesh import setup_sharding
 from .utils import checkpoint as ckpt
 from .utils.config import Config, default_case, load_config
-from .utils.history import HistoryWriter, LatLonHistoryWriter, MetricsLogger
+from .utils.history import HistoryWriter, LatLonHistoryWriter, MetricsLogger, SpectraHistoryWriter
 
 
 # invariants the metrics records gain with the shallow-water model
@@ -242,6 +243,11 @@ class Solver:
         if ll is not None and not (isinstance(ll, (list, tuple)) and len(ll) == 2
                                    and all(isinstance(v, int) and v > 0 for v in ll)):
             raise ValueError(f"io.latlon: [nlat, nlon] of two positive integers expected, not {ll!r}")
+        if c.io.spectra is not None:
+            try:
+                check_lmax(c.io.spectra, N)
+            except ValueError as err:
+                raise ValueError(f"io.spectra: {err}") from None
         self._log(f"Initialized {phys0.name} ({getattr(phys0, 'case', '')}) C{N}, {self.mode} mode, "
                   f"backend={backend}, dtype={c.grid.dtype}, dt={dt:.3f} s, integrator={c.time.integrator}")
         if c.io.initial_condition and not c.io.restore:
@@ -443,6 +449,76 @@ class Solver:
         """[nlat] zonal mean of ``latlon_field(name, nlat, nlon)``."""
         r = self._latlon_arrays([name], nlat, nlon)
         return None if r is None else r[1][0].detach().cpu().numpy()
+
+    # ---- spectra (models/spectra.py, ops/spectra.py) --------------------------------
+    def spectrum_names(self) -> List[str]:
+        """What ``sh_coefficients`` / ``spectrum`` accept for this model."""
+        return list(self.fields) + (list(DERIVED_FIELDS) if self.physics.name == "swe" else [])
+
+    def _spectra_coeffs(self, names, lmax: int, der=None):
+        """Coefficients [len(names), 2, L+1, L+1] float64 of the current state
+        on rank 0, None elsewhere: a tensor on the device (single, virtual) or
+        on the CPU (spmd).  Every rank analyses its own cells and the ranks'
+        arrays are added in ascending rank order (virtual ranks on the device,
+        SPMD ranks on rank 0 after an ``all_gather_object``).  ``der``: the
+        engines' derived fields when the caller has them already
+        (``_derived_all()``).  Collective under SPMD."""
+        for name in names:
+            if name in LATLON_WINDS:
+                raise ValueError(f"{name!r} is a vector component, not a scalar on the sphere: it has no "
+                                 f"spherical-harmonic spectrum; use ke_spectrum for the winds")
+            if name in DERIVED_FIELDS:
+                if self.physics.name != "swe":
+                    raise ValueError(f"derived fields are defined for the shallow-water model, "
+                                     f"not {self.physics.name!r}")
+            elif name not in self.fields:
+                raise ValueError(f"unknown spectrum field {name!r}; choose from {self.spectrum_names()}")
+        sps = [e.spectra(lmax) for e in self.engines]
+        groups = []
+        if any(f in self.fields for f in names):
+            groups.append(("prog", [sp.partial_fields() for sp in sps]))
+        if any(f in DERIVED_FIELDS for f in names):
+            der = self._derived_all() if der is None else der
+            groups.append(("der", [sp.partial_tiles(f) for sp, (f, _) in zip(sps, der)]))
+        done = {}
+        for kind, parts in groups:
+            if self.mode == "spmd":
+                import torch.distributed as dist
+                objs = [None] * self.world
+                dist.all_gather_object(objs, (self.rank, parts[0].detach().cpu().numpy()))
+                if self.rank != 0:
+                    continue
+                parts = [torch.as_tensor(a) for _, a in sorted(objs, key=lambda o: o[0])]
+            done[kind] = sps[0].add_partials(parts)
+        if self.rank != 0:
+            return None
+        return torch.stack([done["prog"][self.fields.index(f)] if f in self.fields
+                            else done["der"][DERIVED_FIELDS.index(f)] for f in names])
+
+    def sh_coefficients(self, name: str, lmax: int) -> Optional[np.ndarray]:
+        """[2, L+1, L+1] real spherical-harmonic coefficients (cos, sin; [l, m])
+        of a prognostic field, ``vorticity``, ``divergence`` or ``pv`` on rank 0
+        (None elsewhere)."""
+        r = self._spectra_coeffs([name], lmax)
+        return None if r is None else r[0].detach().cpu().numpy()
+
+    def spectrum(self, name: str, lmax: int) -> Optional[np.ndarray]:
+        """[L+1] power per degree of ``sh_coefficients(name, lmax)``."""
+        r = self._spectra_coeffs([name], lmax)
+        return None if r is None else spectra_power(r)[0].detach().cpu().numpy()
+
+    def _ke_spectrum(self, lmax: int, der=None):
+        if self.physics.name != "swe":
+            raise ValueError(f"the kinetic-energy spectrum is defined for the shallow-water model, "
+                             f"not {self.physics.name!r}")
+        r = self._spectra_coeffs(["vorticity", "divergence"], lmax, der=der)
+        return None if r is None else spectra_ke(r[0], r[1], self.grid.radius)
+
+    def ke_spectrum(self, lmax: int) -> Optional[np.ndarray]:
+        """[L+1] kinetic energy per degree (m^2 / s^2) from the vorticity and
+        the divergence, on rank 0 (None elsewhere)."""
+        r = self._ke_spectrum(lmax)
+        return None if r is None else r.detach().cpu().numpy()
 
     def invariants(self) -> Dict[str, float]:
         """mass, energy, potential_enstrophy, circulation, abs_circulation
@@ -715,6 +791,13 @@ class Solver:
                                               io.latlon[1], n_out, attrs={"config": self.config, "N": self.layout.N})
         # (writer on rank 0, names) of the lat-lon frames; None: io.latlon unset
         self._latlon_hist = (hll if self.rank == 0 else None, lfields) if hist is not None and io.latlon else None
+        # (writer on rank 0, names) of the spectra frames; None: io.spectra unset
+        self._spectra_hist = None
+        if hist is not None and io.spectra is not None:
+            snames = list(hfields) + (["ke"] if self.physics.name == "swe" else [])
+            hsp = SpectraHistoryWriter(os.path.join(out, "history_spectra.zarr"), snames, io.spectra, n_out,
+                                       attrs={"config": self.config, "N": self.layout.N}) if self.rank == 0 else None
+            self._spectra_hist = (hsp, list(hfields))
         metrics = MetricsLogger(os.path.join(out, "metrics.jsonl") if "metrics" in iv else None,
                                 enabled=self.rank == 0)
         cells = 6 * self.layout.N ** 2
@@ -885,6 +968,38 @@ class Solver:
         pending.append((ev, work))
         if getattr(self, "_latlon_hist", None) is not None:
             self._snapshot_latlon(*self._latlon_hist, k, pending, async_copy, der)
+        if getattr(self, "_spectra_hist", None) is not None:
+            self._snapshot_spectra(*self._spectra_hist, k, pending, async_copy, der)
+
+    def _snapshot_spectra(self, hsp, names, k: int, pending: List[Any], async_copy: bool, der=None) -> None:
+        """Power per degree of history frame k (``io.spectra``): computed on the
+        stepping stream, copied to pinned host memory there and written by the
+        host queue like the frame itself.  Collective under SPMD."""
+        t, sc = self.time, self.step_count
+        L = self.cfg.io.spectra
+        swe = self.physics.name == "swe"
+        if der is None and (swe or any(f in DERIVED_FIELDS for f in names)):
+            der = self._derived_all()
+        r = self._spectra_coeffs(names, L, der=der)
+        ke = self._ke_spectrum(L, der=der) if swe else None
+        if r is None:
+            return
+        v = spectra_power(r)
+        if ke is not None:
+            v = torch.cat([v, ke[None]])
+        v = v.detach()
+        ev = None
+        if async_copy and v.is_cuda:
+            h = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
+            h.copy_(v, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        else:
+            h = v.cpu()
+
+        def work():
+            hsp.write_frame(k, h.double().numpy(), t, sc)
+        pending.append((ev, work))
 
     def _snapshot_latlon(self, hll, names, k: int, pending: List[Any], async_copy: bool, der=None) -> None:
         """Lat-lon arrays of history frame k (``io.latlon``): computed on the

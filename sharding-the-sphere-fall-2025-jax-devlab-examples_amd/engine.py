@@ -91,6 +91,7 @@ class Engine:
         self.step_count = 0
         self.backend = backend
         self._latlon: Dict[tuple, object] = {}      # ops.latlon.LatLon per target grid (latlon())
+        self._spectra: Dict[int, object] = {}       # ops.spectra.Spectra per lmax (spectra())
         self.block = tuple(block) if block is not None else None   # None: ops.hip_compute.choose_block
         if backend == "torch":
             self.compute = TorchCompute(self)
@@ -239,6 +240,16 @@ class Engine:
         if key not in self._latlon:
             self._latlon[key] = LatLon(self, lat, lon)
         return self._latlon[key]
+
+    def spectra(self, lmax: int):
+        """``ops.spectra.Spectra`` of this engine up to degree ``lmax``, built
+        on first use and cached per ``lmax``."""
+        from .models.spectra import check_lmax
+        from .ops.spectra import Spectra
+        key = check_lmax(lmax, self.layout.N)
+        if key not in self._spectra:
+            self._spectra[key] = Spectra(self, key)
+        return self._spectra[key]
 
     def global_field(self, f: int = 0) -> np.ndarray:
         """Single-rank only: [6, N, N] float64 of field f."""

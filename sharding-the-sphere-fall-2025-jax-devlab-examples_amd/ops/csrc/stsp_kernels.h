@@ -233,6 +233,29 @@ typedef struct LatLonDesc {
 } LatLonDesc;
 int stsp_latlon_launch(int dtype, const LatLonDesc* d, hipStream_t stream);
 int stsp_latlon_desc_size(void);
+// Spherical-harmonic analysis (spectra_kernel.hip, ops/spectra.py; definitions,
+// tables and the twin in models/spectra.py): an analysis launch over (order m) x
+// (cell slabs) that leaves one partial record per workgroup, then a fold of the
+// slabs in ascending order.
+typedef struct SpectraDesc {
+  const void* Q;        // source channels [C][cs], element type
+  const int* idx;       // [cells] position of each cell inside a channel (interior slots)
+  const double* cell;   // [cells][4] mu, cos phi, lambda, w (32-byte aligned)
+  const double* a;      // [L+1][L+1] recurrence factors a[l][m] (0 where l <= m)
+  const double* b;      // [L+1][L+1]
+  const double* c;      // [L+1] sectoral factors: P_mm = c[m] cos^m phi
+  double* partial;      // [slabs][L+1][RP][16] workgroup records, row l - m, column 2 ch + (sin)
+  double* out;          // [C][2][L+1][L+1] coefficients at [l][m]; the caller zero-fills it
+  long long cs;         // channel stride of Q in elements
+  int cells;            // cells of the rank
+  int C;                // channels, 1 .. 8
+  int lmax;             // L, 0 .. 1023
+  int slabs;            // cell slabs (grid y), none empty
+  int slab_cells;       // cells per slab, a multiple of 128
+  int RP;               // rows per record: a multiple of 32, >= L + 1
+} SpectraDesc;
+int stsp_spectra_launch(int dtype, const SpectraDesc* d, hipStream_t stream);
+int stsp_spectra_desc_size(void);
 // Direct xGMI halo build constant: ring slots.
 int stsp_xg_slots(void);
 }

@@ -108,6 +108,18 @@ class LatLonDesc(ctypes.Structure):
     ]
 
 
+class SpectraDesc(ctypes.Structure):
+    """Mirror of SpectraDesc (stsp_kernels.h): spherical-harmonic analysis."""
+    _fields_ = [
+        ("Q", ctypes.c_void_p), ("idx", ctypes.c_void_p), ("cell", ctypes.c_void_p),
+        ("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("c", ctypes.c_void_p),
+        ("partial", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("cs", ctypes.c_longlong),
+        ("cells", ctypes.c_int), ("C", ctypes.c_int), ("lmax", ctypes.c_int),
+        ("slabs", ctypes.c_int), ("slab_cells", ctypes.c_int), ("RP", ctypes.c_int),
+    ]
+
+
 def lib_path() -> str:
     return _build.lib_for(os.environ.get("STSP_VARIANT", ""))
 
@@ -162,6 +174,13 @@ def load(build_if_missing: bool = True):
         if L.stsp_latlon_desc_size() != ctypes.sizeof(LatLonDesc):
             raise RuntimeError(f"LatLonDesc: ctypes mirror is {ctypes.sizeof(LatLonDesc)} bytes, "
                                f"the library's {L.stsp_latlon_desc_size()} (stale libstsp.so?)")
+        L.stsp_spectra_launch.argtypes = [ci, ctypes.POINTER(SpectraDesc), vp]
+        L.stsp_spectra_launch.restype = ci
+        L.stsp_spectra_desc_size.argtypes = []
+        L.stsp_spectra_desc_size.restype = ci
+        if L.stsp_spectra_desc_size() != ctypes.sizeof(SpectraDesc):
+            raise RuntimeError(f"SpectraDesc: ctypes mirror is {ctypes.sizeof(SpectraDesc)} bytes, "
+                               f"the library's {L.stsp_spectra_desc_size()} (stale libstsp.so?)")
         _declare_runtime(L)
         _declare_tt(L)
         L.stsp_schedule_spin.argtypes = [ci]

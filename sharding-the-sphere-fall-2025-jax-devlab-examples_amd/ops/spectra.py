@@ -1,0 +1,124 @@
+"""Spherical-harmonic analysis of an engine's fields (models/spectra.py).
+
+``Spectra(engine, lmax)`` owns the rank's tables (mu, cos phi, lambda, w per
+cell; the recurrence factors), one index table per source layout (the padded
+state [F, T P P] and the unpadded [C, T, n, n] that ``DerivedFields.compute``
+returns), the workgroup records and the kernel descriptor.  With
+``backend='hip'`` on a GPU the analysis is two ordinary launches of
+``ops/csrc/spectra_kernel.hip`` on the caller's stream; with
+``backend='torch'``, or on a CPU device, it runs the PyTorch twin.  No ghost
+slot is ever read.
+
+One rank:   ``partial_fields(q)`` / ``partial_tiles(x)`` are the coefficients
+            [C, 2, L+1, L+1] float64 (cos, sin; [l, m]).
+Several:    every rank's partial is the sum over its own cells; the ranks'
+            arrays are added in ascending rank order (``add_partials``).
+
+All shape contracts the kernel relies on are checked here, on the host, before
+anything is launched.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import torch
+
+from ..models import spectra as ms
+
+BATCH = 128            # cells per batch of the kernel (its workgroup size)
+GROUP = 32             # degrees per group
+
+
+class Spectra:
+    def __init__(self, engine, lmax: int):
+        e = self.e = engine
+        plan = e.plan
+        self.lmax = L = ms.check_lmax(lmax, e.layout.N)
+        self.tab = ms.rank_tables(e.geo, L, e.device)
+        self.S = plan.S
+        self.cells = plan.T * plan.n * plan.n
+        pad, unp = ms.rank_index(plan)
+        self.pad = torch.as_tensor(pad, device=e.device)
+        self.unp = torch.as_tensor(unp, device=e.device)
+        self.hip = e.backend == "hip" and e.device.type == "cuda"
+        # ---- host-side shape contract checks ------------------------------------
+        t = self.tab
+        assert t.cells == self.cells and self.cells >= 1
+        assert t.cell.dtype == torch.float64 and t.cell.shape == (self.cells, 4) and t.cell.is_contiguous()
+        for x in (t.a, t.b):
+            assert x.dtype == torch.float64 and x.shape == (L + 1, L + 1) and x.is_contiguous()
+        assert t.c.dtype == torch.float64 and t.c.shape == (L + 1,)
+        for ix, lim in ((self.pad, self.S), (self.unp, self.cells)):
+            assert ix.dtype == torch.int32 and ix.shape == (self.cells,) and ix.is_contiguous()
+            assert int(ix.min()) >= 0 and int(ix.max()) < lim
+        # the padded table addresses interior cells only
+        P, g, n = plan.P, plan.ng, plan.n
+        i = self.pad.long() % (P * P)
+        x, y = i % P, i // P
+        assert bool(((x >= g) & (x < g + n) & (y >= g) & (y < g + n)).all())
+        if self.hip:
+            from . import native
+            self.lib = native.require_native()
+            self.dcode = native.dtype_code(e.dtype)
+            assert t.cell.data_ptr() % 32 == 0
+            # slabs: a grid of about twice the compute units, every slab whole batches, none empty
+            cus = torch.cuda.get_device_properties(e.device).multi_processor_count
+            nbatch = -(-self.cells // BATCH)
+            want = max(1, min(nbatch, round(2 * cus / (L + 1)), 65535))
+            per = -(-nbatch // want)
+            self.slab_cells = per * BATCH
+            self.slabs = -(-nbatch // per)
+            assert (self.slabs - 1) * self.slab_cells < self.cells <= self.slabs * self.slab_cells
+            self.RP = -(-(L + 1) // GROUP) * GROUP
+            self.partial = torch.empty((self.slabs, L + 1, self.RP, 16), dtype=torch.float64, device=e.device)
+
+    # ---- kernel ----------------------------------------------------------------------
+    def _analyse(self, x: torch.Tensor, idx: torch.Tensor, lim: int) -> torch.Tensor:
+        from . import native
+        e, t, L = self.e, self.tab, self.lmax
+        if x.dim() != 2 or x.shape[1] != lim:
+            raise ValueError(f"spectra: [C, {lim}] expected, not {tuple(x.shape)}")
+        C = x.shape[0]
+        if not 1 <= C <= ms.MAX_CHANNELS:
+            raise ValueError(f"spectra: 1 .. {ms.MAX_CHANNELS} channels per call, not {C}")
+        assert x.is_contiguous() and x.dtype == e.dtype and x.is_cuda
+        out = torch.zeros((C, 2, L + 1, L + 1), dtype=torch.float64, device=e.device)
+        d = native.SpectraDesc()
+        d.Q, d.idx, d.cell = native.ptr(x), native.ptr(idx), native.ptr(t.cell)
+        d.a, d.b, d.c = native.ptr(t.a), native.ptr(t.b), native.ptr(t.c)
+        d.partial, d.out = native.ptr(self.partial), native.ptr(out)
+        d.cs, d.cells, d.C, d.lmax = lim, self.cells, C, L
+        d.slabs, d.slab_cells, d.RP = self.slabs, self.slab_cells, self.RP
+        native.check(self.lib.stsp_spectra_launch(self.dcode, d, native.current_stream_handle(e.device)),
+                     "spectra kernel")
+        return out
+
+    # ---- this rank's part of the coefficients: [C, 2, L+1, L+1] float64 --------------------
+    def partial_fields(self, q: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Every channel of the padded state ``q`` [F, S] (default: the engine's)."""
+        q = self.e.state if q is None else q
+        if self.hip:
+            return self._analyse(q, self.pad, self.S)
+        if q.dim() != 2 or q.shape[1] != self.S:
+            raise ValueError(f"spectra: [C, {self.S}] expected, not {tuple(q.shape)}")
+        return ms.analyse(q[:, self.pad.long()], self.tab)
+
+    def partial_tiles(self, x: torch.Tensor) -> torch.Tensor:
+        """The channels of an unpadded array ``x`` [C, T, n, n]."""
+        x = x.reshape(x.shape[0], -1)
+        if self.hip:
+            return self._analyse(x.contiguous(), self.unp, self.cells)
+        return ms.analyse(x, self.tab)
+
+    @staticmethod
+    def add_partials(parts: Sequence[torch.Tensor]) -> torch.Tensor:
+        """The ranks' partials, given in ascending rank order, added in that order."""
+        acc = parts[0]
+        for p in parts[1:]:
+            acc = acc + p
+        return acc
+
+    @staticmethod
+    def power(coeffs: torch.Tensor) -> torch.Tensor:
+        """[C, L+1] power per degree of the coefficients [C, 2, L+1, L+1]."""
+        return ms.power(coeffs)

@@ -80,6 +80,10 @@ class IOConfig:
     # [nlat, nlon]: every history frame is also written on the cell-centred
     # lat-lon grid, to history_latlon.zarr (models/latlon.py); null = off
     latlon: Optional[List[int]] = None
+    # L: every history frame's power per degree 0 .. L (and the kinetic-energy
+    # spectrum of the shallow-water model) goes to history_spectra.zarr
+    # (models/spectra.py); null = off
+    spectra: Optional[int] = None
 
 
 @dataclass

@@ -113,6 +113,39 @@ class LatLonHistoryWriter:
         zarr_lite.write_chunk(self.path, "step", (0,), self._steps, meta=self._meta["step"])
 
 
+class SpectraHistoryWriter:
+    """Power per degree of the history frames (``io.spectra``):
+
+        history_spectra.zarr/<name>   shape (n_out, L+1): the fields, ``ke``
+        history_spectra.zarr/degree   0 .. L
+        history_spectra.zarr/time, step
+
+    written whole, frame by frame, by rank 0."""
+
+    def __init__(self, path: str, names: List[str], lmax: int, n_out: int, attrs: Optional[Dict[str, Any]] = None):
+        self.path, self.names, self.n_out = path, list(names), n_out
+        zarr_lite.create_group(path, attrs=dict(attrs or {}, fields=self.names, lmax=lmax))
+        for f in self.names:
+            zarr_lite.create_array(path, f, (n_out, lmax + 1), np.float64, chunks=(1, lmax + 1))
+        zarr_lite.write_array(path, "degree", np.arange(lmax + 1, dtype=np.int64))
+        zarr_lite.create_array(path, "time", (n_out,), np.float64, chunks=(n_out,))
+        zarr_lite.create_array(path, "step", (n_out,), np.int64, chunks=(n_out,))
+        self._meta = {f: zarr_lite.array_meta(path, f) for f in self.names + ["time", "step"]}
+        self._times = np.zeros(n_out)
+        self._steps = np.zeros(n_out, dtype=np.int64)
+
+    def write_frame(self, k: int, values: np.ndarray, t: float, step: int) -> None:
+        """values [len(names), L+1] for history slot k."""
+        if k >= self.n_out:
+            return
+        for j, name in enumerate(self.names):
+            zarr_lite.write_chunk(self.path, name, (k, 0), values[j][None], meta=self._meta[name])
+        self._times[k] = t
+        self._steps[k] = step
+        zarr_lite.write_chunk(self.path, "time", (0,), self._times, meta=self._meta["time"])
+        zarr_lite.write_chunk(self.path, "step", (0,), self._steps, meta=self._meta["step"])
+
+
 def read_history(path: str, field: str) -> np.ndarray:
     return zarr_lite.read_array(path, field)
 

@@ -7,6 +7,7 @@ s.4, s.12, s.13, s.17, s.18).
                     (cosine bell, PDF s.13)
 * ``latlon_image``  image of a field regridded to a lat-lon grid (models/latlon.py)
                     beside its zonal-mean profile
+* ``spectrum_plot`` log-log power per degree or kinetic-energy spectrum (models/spectra.py)
 * ``six_panel``     per-face images of an initial and a final field
                     (PDF s.18 "Initial vs Final")
 * ``mesh_plot``     the cubed-sphere dual mesh outline (PDF s.4)
@@ -126,6 +127,29 @@ def mesh_plot(grid: CubedSphereGrid, path: str, stride: int = 1) -> str:
     ax.set_box_aspect((1, 1, 1))
     ax.set_axis_off()
     ax.set_title(f"Cube sphere mesh (Ne={grid.N}x{grid.N}, {6 * grid.N * grid.N} quads)")
+    fig.savefig(path, dpi=110, bbox_inches="tight")
+    plt.close(fig)
+    return path
+
+
+def spectrum_plot(spec: np.ndarray, path: str, title: str = "", ylabel: str = "power per degree",
+                  labels: Optional[Sequence[str]] = None) -> str:
+    """Log-log image of a spectrum [L+1] (or several [K, L+1]: one line each)
+    against the degree l = 1 .. L (``Solver.spectrum`` / ``ke_spectrum``,
+    models/spectra.py); degree 0 and non-positive values are left out."""
+    plt = _plt()
+    s = np.atleast_2d(np.asarray(spec, dtype=np.float64))
+    l = np.arange(s.shape[1])
+    fig, ax = plt.subplots(figsize=(6.5, 4.5))
+    for k, row in enumerate(s):
+        ok = (l >= 1) & (row > 0)
+        ax.loglog(l[ok], row[ok], marker=".", lw=1.0, label=None if labels is None else labels[k])
+    ax.set_xlabel("spherical-harmonic degree l")
+    ax.set_ylabel(ylabel)
+    ax.grid(True, which="both", lw=0.3, alpha=0.5)
+    if labels is not None:
+        ax.legend(fontsize=8)
+    ax.set_title(title)
     fig.savefig(path, dpi=110, bbox_inches="tight")
     plt.close(fig)
     return path
