@@ -17,6 +17,11 @@
     spectrum HISTORY.zarr FIELD LMAX OUT.npz           power per degree 0 .. LMAX of a history field (``ke``:
                                                        the kinetic-energy spectrum of a shallow-water
                                                        history), on the CPU
+    synth HISTORY.zarr FIELD LMAX OUT.npz [--band LMIN LCUT]
+                                                       a history field analysed to degree LMAX and synthesised
+                                                       back on the cells (--band: degrees LMIN .. LCUT only), or
+                                                       the streamfunction / velocity_potential of a
+                                                       shallow-water history, on the CPU
     ensemble CONFIG.yaml [--members M] [--amplitude A] [--days D | --nsteps K]
                                                        perturbed members of one config on one device
     build                                              compile the gfx950 library
@@ -66,6 +71,13 @@ def main(argv=None):
     sp.add_argument("field")
     sp.add_argument("lmax", type=int)
     sp.add_argument("out")
+    sy = sub.add_parser("synth")
+    sy.add_argument("history")
+    sy.add_argument("field")
+    sy.add_argument("lmax", type=int)
+    sy.add_argument("out")
+    sy.add_argument("--band", type=int, nargs=2, metavar=("LMIN", "LCUT"), default=None,
+                    help="keep the degrees LMIN .. LCUT only")
     en = sub.add_parser("ensemble")
     en.add_argument("config")
     en.add_argument("--members", type=int, default=2)
@@ -115,6 +127,12 @@ def main(argv=None):
         r = spectrum_history(a.history, a.field, a.lmax)
         np.savez(a.out, **r)
         print(json.dumps({"out": a.out, "field": a.field, "shape": list(r["spectrum"].shape)}))
+        return 0
+    if a.cmd == "synth":
+        import numpy as np
+        r = synth_history(a.history, a.field, a.lmax, band=a.band)
+        np.savez(a.out, **r)
+        print(json.dumps({"out": a.out, "field": a.field, "shape": list(r["field"].shape)}))
         return 0
     if a.cmd == "regrid":
         import numpy as np
@@ -248,6 +266,55 @@ def spectrum_history(history: str, field: str, lmax: int) -> dict:
             out.append(ms.power(ms.analyse(fr.reshape(1, -1), tb))[0])
     return {"spectrum": torch.stack(out).numpy(), "degree": np.arange(lmax + 1),
             "time": zarr_lite.read_array(history, "time")}
+
+
+def synth_history(history: str, field: str, lmax: int, band=None) -> dict:
+    """Every frame of a history field analysed to degree ``lmax``, its degrees
+    outside ``band`` = (lmin, lcut) dropped, and synthesised back on the cells
+    with the PyTorch twin on the CPU (models/spectra.py): field [frames, 6, N, N],
+    time.  ``streamfunction`` / ``velocity_potential``: psi / chi (m^2 / s) from
+    the h, mx, my, mz of a shallow-water history (vorticity and divergence by
+    the derived-field twin)."""
+    import numpy as np
+    import torch
+    from .models import spectra as ms
+    from .models.geometry import EARTH_RADIUS, CubedSphereGrid
+    from .utils import zarr_lite
+    have = zarr_lite.list_arrays(history)
+    if field in ("u", "v") and field not in have:
+        raise ValueError(f"{field!r} is a vector component, not a scalar on the sphere; use the fields "
+                         f"'streamfunction' and 'velocity_potential' for the winds")
+    hel = field in ("streamfunction", "velocity_potential") and field not in have
+    need = ["h", "mx", "my", "mz"] if hel else [field]
+    missing = [f for f in need if f not in have]
+    if missing:
+        raise ValueError(f"{history}: no array {missing} (it holds {[f for f in have if f not in ('time', 'step')]})")
+    src = np.stack([zarr_lite.read_array(history, f) for f in need], 1)       # [frames, C, 6, N, N]
+    N = src.shape[-1]
+    cfg = (zarr_lite.read_attrs(history).get("config") or {})
+    radius = (cfg.get("grid") or {}).get("radius") or EARTH_RADIUS
+    grid = CubedSphereGrid(N, radius)
+    lmax = ms.check_lmax(lmax, N)
+    fac = ms.band_factors(lmax) if band is None else ms.band_factors(lmax, band[0], band[1])
+    out = []
+    if hel:
+        from .engine import Engine
+        from .models.swe import ShallowWater
+        from .parallel.layout import TileLayout
+        e = Engine(ShallowWater((cfg.get("physics") or {}).get("case") or "tc5"), TileLayout(N, 1, 1, ng=2), grid=grid)
+        sp = e.spectra(lmax)
+        which = 0 if field == "streamfunction" else 1
+        for fr in torch.as_tensor(np.ascontiguousarray(src, dtype=np.float64)):
+            e.set_state(fr)
+            c = sp.partial_tiles(e.derived()[0][:2])
+            co = ms.scale_degrees(ms.helmholtz(c[0], c[1], radius)[which], fac)
+            out.append(sp.synthesise(co[None])[0])
+    else:
+        tb = ms.grid_tables(grid, lmax)
+        for fr in torch.as_tensor(np.ascontiguousarray(src, dtype=np.float64)):
+            co = ms.scale_degrees(ms.analyse(fr.reshape(1, -1), tb), fac)
+            out.append(ms.synthesise(ms.clean_coeffs(co), tb)[0].reshape(6, N, N))
+    return {"field": torch.stack(out).numpy(), "time": zarr_lite.read_array(history, "time")}
 
 
 def run_ensemble(config, members: int, amplitude: float, days=None, nsteps=None) -> dict:

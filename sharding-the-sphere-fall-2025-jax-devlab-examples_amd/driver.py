@@ -37,6 +37,8 @@ from .models.derived import FIELDS as DERIVED_FIELDS, INVARIANTS
 from .models.diffusion import Diffusion
 from .models.geometry import DAY, EARTH_RADIUS, CubedSphereGrid
 from .models.spectra import check_lmax, ke_spectrum as spectra_ke, power as spectra_power
+from .models.spectra import (MAX_CHANNELS as spectra_max_channels, band_factors as spectra_band,
+                             helmholtz as spectra_helmholtz, scale_degrees as spectra_scale)
 from .models.swe import ShallowWater
 from .parallel.comm import NativeBuffers, TorchDistTransport
 from .parallel.layout import TileLayout
@@ -519,6 +521,95 @@ class Solver:
         the divergence, on rank 0 (None elsewhere)."""
         r = self._ke_spectrum(lmax)
         return None if r is None else r.detach().cpu().numpy()
+
+    # ---- synthesis: filters, psi and chi (models/spectra.py, ops/spectra.py) ---------------
+    def _synthesise(self, coeffs, lmax: int) -> Optional[np.ndarray]:
+        """[C, 6, N, N] float64 on rank 0 (None elsewhere) of the coefficients
+        [C, 2, L+1, L+1] that rank 0 holds (a tensor; ignored elsewhere).  Under
+        SPMD they are broadcast from rank 0; every rank synthesises its own
+        cells and the tiles are gathered as ``derived_field`` gathers them.
+        Collective under SPMD."""
+        sps = [e.spectra(lmax) for e in self.engines]
+        if self.mode == "spmd":
+            import torch.distributed as dist
+            box = [coeffs.detach().cpu().numpy() if self.rank == 0 else None]
+            dist.broadcast_object_list(box, src=0)
+            coeffs = torch.as_tensor(box[0])
+        C = coeffs.shape[0]
+        vals = {}
+        for e, sp in zip(self.engines, sps):
+            # at most 8 channels per launch
+            parts = [sp.synthesise(coeffs[k:k + spectra_max_channels].contiguous())
+                     for k in range(0, C, spectra_max_channels)]
+            vals[e.rank] = torch.cat(parts).detach().cpu().numpy()
+        if self.mode == "spmd":
+            import torch.distributed as dist
+            objs = [None] * self.world
+            dist.all_gather_object(objs, vals)
+            vals = {}
+            for o in objs:
+                vals.update(o)
+            if self.rank != 0:
+                return None
+        return np.stack([assemble_global(self.layout, {r: v[k] for r, v in vals.items()}) for k in range(C)])
+
+    def synthesise(self, coeffs) -> Optional[np.ndarray]:
+        """The band-limited field of given real spherical-harmonic coefficients
+        on the solver's own cells: [6, N, N] for ``coeffs`` [2, L+1, L+1] (cos,
+        sin; [l, m]), [C, 6, N, N] for [C, 2, L+1, L+1]; float64, on rank 0
+        (None elsewhere).  Every rank passes the same array.  Entries with
+        m > l and S_l0 are not read."""
+        co = torch.as_tensor(np.asarray(coeffs, dtype=np.float64))
+        one = co.dim() == 3
+        if one:
+            co = co[None]
+        if co.dim() != 4 or co.shape[0] < 1 or co.shape[1] != 2 or co.shape[2] != co.shape[3]:
+            raise ValueError(f"synthesise: coefficients [2, L+1, L+1] or [C, 2, L+1, L+1] expected, "
+                             f"not {tuple(np.shape(coeffs))}")
+        lmax = check_lmax(int(co.shape[2]) - 1, self.layout.N)
+        r = self._synthesise(co.to(self.engines[0].device), lmax)
+        return None if r is None else (r[0] if one else r)
+
+    def filtered_field(self, name: str, lmax: int, factors) -> Optional[np.ndarray]:
+        """[6, N, N] float64 on rank 0 (None elsewhere): the field ``name``
+        (anything in ``spectrum_names()``) analysed to degree ``lmax``, its
+        coefficients of degree l multiplied by ``factors[l]`` ([L+1]; see
+        ``band_factors`` / ``exp_factors`` in models/spectra.py) and synthesised
+        on the solver's cells."""
+        f = torch.as_tensor(np.asarray(factors, dtype=np.float64))
+        lmax = check_lmax(lmax, self.layout.N)
+        if f.shape != (lmax + 1,):
+            raise ValueError(f"filtered_field: factors [{lmax + 1}] expected, not {tuple(f.shape)}")
+        r = self._spectra_coeffs([name], lmax)
+        co = None if r is None else spectra_scale(r, f.to(r.device))
+        r = self._synthesise(co, lmax)
+        return None if r is None else r[0]
+
+    def band_field(self, name: str, lmax: int, lmin: int = 0, lcut: Optional[int] = None) -> Optional[np.ndarray]:
+        """``filtered_field`` with the degrees ``lmin .. lcut`` (default: up to
+        ``lmax``) kept and the others dropped: a low-, high- or band-pass view."""
+        lmax = check_lmax(lmax, self.layout.N)
+        return self.filtered_field(name, lmax, spectra_band(lmax, lmin, lcut))
+
+    def _psi_chi(self, lmax: int, which: int, what: str) -> Optional[np.ndarray]:
+        if self.physics.name != "swe":
+            raise ValueError(f"the {what} is defined for the shallow-water model, "
+                             f"not {self.physics.name!r}")
+        r = self._spectra_coeffs(["vorticity", "divergence"], lmax)
+        co = None if r is None else spectra_helmholtz(r[0], r[1], self.grid.radius)[which][None]
+        r = self._synthesise(co, check_lmax(lmax, self.layout.N))
+        return None if r is None else r[0]
+
+    def streamfunction(self, lmax: int) -> Optional[np.ndarray]:
+        """[6, N, N] streamfunction psi (m^2 / s), psi_lm = -R^2 zeta_lm / (l (l+1))
+        to degree ``lmax`` (v = k x grad psi + grad chi), on rank 0 (None
+        elsewhere)."""
+        return self._psi_chi(lmax, 0, "streamfunction")
+
+    def velocity_potential(self, lmax: int) -> Optional[np.ndarray]:
+        """[6, N, N] velocity potential chi (m^2 / s) from the divergence, like
+        ``streamfunction``."""
+        return self._psi_chi(lmax, 1, "velocity potential")
 
     def invariants(self) -> Dict[str, float]:
         """mass, energy, potential_enstrophy, circulation, abs_circulation

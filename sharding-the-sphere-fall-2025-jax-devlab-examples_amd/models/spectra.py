@@ -223,3 +223,131 @@ def sample_harmonic(tb: SpectraTables, l: int, m: int, part: str = "c") -> torch
     co = torch.zeros((1, 2, tb.lmax + 1, tb.lmax + 1), dtype=torch.float64, device=tb.cell.device)
     co[0, 0 if part == "c" else 1, l, m] = 1.0
     return synthesise(co, tb)[0]
+
+
+# ----------------------------------------------------------------------------
+# synthesis: degree factors, psi and chi, and what ops/csrc/synth_kernel.hip reads
+# ----------------------------------------------------------------------------
+# Sign convention: v = k x grad psi + grad chi, so zeta = lap psi and delta = lap chi;
+# with lap Y_lm = -l (l+1) / R^2 Y_lm that is psi_lm = -R^2 zeta_lm / (l (l+1)) and
+# likewise chi from delta.  The degree 0 of psi and chi is arbitrary and set to 0.
+
+def _check_factor_lmax(lmax) -> int:
+    if not isinstance(lmax, (int, np.integer)) or isinstance(lmax, bool) or lmax < 0:
+        raise ValueError(f"lmax: a non-negative integer expected, not {lmax!r}")
+    return int(lmax)
+
+
+def band_factors(lmax: int, lmin: int = 0, lcut: Optional[int] = None) -> torch.Tensor:
+    """[L+1] float64: 1 for lmin <= l <= lcut (default: lmax), 0 outside."""
+    L = _check_factor_lmax(lmax)
+    lcut = L if lcut is None else lcut
+    for name, v in (("lmin", lmin), ("lcut", lcut)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+            raise ValueError(f"{name}: an integer expected, not {v!r}")
+    if not 0 <= lmin <= lcut:
+        raise ValueError(f"band {lmin} .. {lcut}: 0 <= lmin <= lcut expected")
+    l = torch.arange(L + 1)
+    return ((l >= lmin) & (l <= lcut)).to(torch.float64)
+
+
+def exp_factors(lmax: int, lcut: int, order: int = 2) -> torch.Tensor:
+    """[L+1] float64: the exponential low-pass exp(-(l (l+1) / (lcut (lcut+1)))^order)."""
+    L = _check_factor_lmax(lmax)
+    if lcut < 1 or order < 1:
+        raise ValueError(f"exp_factors: lcut >= 1 and order >= 1 expected, not {lcut}, {order}")
+    l = torch.arange(L + 1, dtype=torch.float64)
+    return torch.exp(-((l * (l + 1.0)) / (lcut * (lcut + 1.0))) ** order)
+
+
+def inverse_laplacian_factors(lmax: int, radius: float) -> torch.Tensor:
+    """[L+1] float64: -R^2 / (l (l+1)), 0 at l = 0."""
+    L = _check_factor_lmax(lmax)
+    l = torch.arange(L + 1, dtype=torch.float64)
+    return torch.where(l > 0, -(radius * radius) / (l * (l + 1.0)).clamp_min(1.0), torch.zeros_like(l))
+
+
+def scale_degrees(coeffs: torch.Tensor, factors) -> torch.Tensor:
+    """``coeffs`` [..., L+1, L+1] ([l, m]) times ``factors`` [L+1] along l."""
+    f = torch.as_tensor(factors, dtype=torch.float64, device=coeffs.device)
+    if coeffs.dim() < 2 or f.shape != (coeffs.shape[-2],) or coeffs.shape[-1] != coeffs.shape[-2]:
+        raise ValueError(f"scale_degrees: coefficients [..., L+1, L+1] and factors [L+1] expected, "
+                         f"not {tuple(coeffs.shape)} and {tuple(f.shape)}")
+    return coeffs * f[:, None]
+
+
+def helmholtz(zeta: torch.Tensor, delta: torch.Tensor, radius: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(psi, chi) coefficients (m^2 / s) from those of the relative vorticity
+    and the divergence, [..., L+1, L+1] each."""
+    assert zeta.shape == delta.shape
+    f = inverse_laplacian_factors(zeta.shape[-2] - 1, radius).to(zeta.device)
+    return scale_degrees(zeta, f), scale_degrees(delta, f)
+
+
+def packed_rows(lmax: int) -> int:
+    return (lmax + 1) * (lmax + 2) // 2
+
+
+def pack_index(lmax: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(l, m) int64 [R] of the packed rows: every (m, l >= m) in order of m, then
+    l; R = (L+1)(L+2)/2 and the row of (m, l) is m (L+1) - m (m-1) / 2 + l - m."""
+    L = int(lmax)
+    m = np.repeat(np.arange(L + 1), L + 1 - np.arange(L + 1))
+    start = np.arange(L + 1) * (L + 1) - np.arange(L + 1) * (np.arange(L + 1) - 1) // 2
+    l = np.arange(packed_rows(L)) - start[m] + m
+    return l.astype(np.int64), m.astype(np.int64)
+
+
+def pack_coeffs(coeffs: torch.Tensor, index=None) -> torch.Tensor:
+    """What the synthesis kernel reads: [R, 16] float64, column 2 ch + s of row
+    (m, l) = ``coeffs[ch, s, l, m]``; 0 in the columns beyond 2 C and in the sine
+    column of m = 0 (sin 0 = 0).  A gather of the lower triangle: entries with
+    m > l and S_l0 are never read.  ``index``: ``pack_index`` as long tensors on
+    the coefficients' device, when the caller keeps them."""
+    C, L = coeffs.shape[0], coeffs.shape[-1] - 1
+    assert coeffs.shape == (C, 2, L + 1, L + 1) and 1 <= C <= MAX_CHANNELS and coeffs.dtype == torch.float64
+    if index is None:
+        index = tuple(torch.as_tensor(x, device=coeffs.device) for x in pack_index(L))
+    l, m = index
+    out = torch.zeros((l.shape[0], 2 * MAX_CHANNELS), dtype=torch.float64, device=coeffs.device)
+    out[:, :2 * C] = coeffs[:, :, l, m].permute(2, 0, 1).reshape(l.shape[0], 2 * C)
+    out[:L + 1, 1::2] = 0.0                           # order 0 is the first L + 1 rows
+    return out
+
+
+def unpack_coeffs(packed: torch.Tensor, C: int, lmax: int) -> torch.Tensor:
+    """The inverse of ``pack_coeffs``: [C, 2, L+1, L+1] with zeros at m > l and in S_l0."""
+    L = int(lmax)
+    l, m = (torch.as_tensor(x, device=packed.device) for x in pack_index(L))
+    assert packed.shape == (l.shape[0], 2 * MAX_CHANNELS)
+    out = torch.zeros((C, 2, L + 1, L + 1), dtype=torch.float64, device=packed.device)
+    out[:, :, l, m] = packed[:, :2 * C].reshape(l.shape[0], C, 2).permute(1, 2, 0)
+    return out
+
+
+def chunk_bounds(lmax: int, chunks: int) -> list:
+    """[chunks + 1] first order of each chunk of the synthesis launch, 0 = b[0] <
+    b[1] < ... < b[chunks] = L + 1: contiguous, none empty, and about equal
+    numbers of (degree, order) rows each (order m has L + 1 - m)."""
+    L = int(lmax)
+    if not isinstance(chunks, (int, np.integer)) or isinstance(chunks, bool) or not 1 <= chunks <= L + 1:
+        raise ValueError(f"chunks = {chunks!r} outside 1 .. {L + 1}")
+    total = packed_rows(L)
+    b, m, done = [0], 0, 0
+    for k in range(1, chunks):
+        # at least one order, and leave one for each chunk still to come
+        m, done = m + 1, done + (L + 1 - m)
+        while done * chunks < k * total and m < L + 1 - (chunks - k):
+            done += L + 1 - m
+            m += 1
+        b.append(m)
+    b.append(L + 1)
+    return b
+
+
+def clean_coeffs(coeffs: torch.Tensor) -> torch.Tensor:
+    """``coeffs`` [C, 2, L+1, L+1] with +0 at m > l and in S_l0: what a synthesis
+    reads of it."""
+    co = torch.tril(coeffs)
+    co[:, 1, :, 0] = 0.0
+    return co

@@ -256,6 +256,32 @@ typedef struct SpectraDesc {
 } SpectraDesc;
 int stsp_spectra_launch(int dtype, const SpectraDesc* d, hipStream_t stream);
 int stsp_spectra_desc_size(void);
+// Spherical-harmonic synthesis (synth_kernel.hip, ops/spectra.py; packing, chunk
+// bounds and the twin in models/spectra.py): a launch over (cell batches of 128) x
+// (order chunks); with more than one chunk every workgroup leaves a record and a
+// fold adds the chunks in ascending order.
+typedef struct SynthDesc {
+  const double* K;        // packed coefficients [k_rows][16]: row of (m, l >= m) = m (L+1) - m (m-1) / 2 + l - m
+  const int* idx;         // [cells] position of each cell inside a channel of out, all < idx_limit
+  const double* cell;     // [cells][4] mu, cos phi, lambda, w (32-byte aligned)
+  const double* a;        // [L+1][L+1] recurrence factors, transposed: a[m][l] (0 where l <= m)
+  const double* b;        // [L+1][L+1] likewise b[m][l]
+  const double* c;        // [L+1] sectoral factors: P_mm = c[m] cos^m phi
+  const int* bounds;      // host: [chunks + 1] first order of each chunk, 0 = b[0] < ... < b[chunks] = L + 1
+  const int* bounds_dev;  // the same numbers in device memory
+  double* rec;            // [chunks][C][cells] workgroup records (unused, nullable, with one chunk)
+  double* out;            // [C][cells] the field, float64
+  long long k_rows;       // (L+1)(L+2)/2
+  long long rec_elems;    // elements rec holds, >= chunks C cells
+  int cells;              // cells of the rank
+  int idx_limit;          // what the host checked idx against: must equal cells
+  int C;                  // channels, 1 .. 8
+  int lmax;               // L, 0 .. 1023
+  int chunks;             // order chunks (grid y), 1 .. L + 1
+  int pad_;
+} SynthDesc;
+int stsp_synth_launch(const SynthDesc* d, hipStream_t stream);
+int stsp_synth_desc_size(void);
 // Direct xGMI halo build constant: ring slots.
 int stsp_xg_slots(void);
 }

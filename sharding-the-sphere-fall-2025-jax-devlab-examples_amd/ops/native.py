@@ -120,6 +120,19 @@ class SpectraDesc(ctypes.Structure):
     ]
 
 
+class SynthDesc(ctypes.Structure):
+    """Mirror of SynthDesc (stsp_kernels.h): spherical-harmonic synthesis."""
+    _fields_ = [
+        ("K", ctypes.c_void_p), ("idx", ctypes.c_void_p), ("cell", ctypes.c_void_p),
+        ("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("c", ctypes.c_void_p),
+        ("bounds", ctypes.c_void_p), ("bounds_dev", ctypes.c_void_p),
+        ("rec", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("k_rows", ctypes.c_longlong), ("rec_elems", ctypes.c_longlong),
+        ("cells", ctypes.c_int), ("idx_limit", ctypes.c_int), ("C", ctypes.c_int), ("lmax", ctypes.c_int),
+        ("chunks", ctypes.c_int), ("pad_", ctypes.c_int),
+    ]
+
+
 def lib_path() -> str:
     return _build.lib_for(os.environ.get("STSP_VARIANT", ""))
 
@@ -181,6 +194,13 @@ def load(build_if_missing: bool = True):
         if L.stsp_spectra_desc_size() != ctypes.sizeof(SpectraDesc):
             raise RuntimeError(f"SpectraDesc: ctypes mirror is {ctypes.sizeof(SpectraDesc)} bytes, "
                                f"the library's {L.stsp_spectra_desc_size()} (stale libstsp.so?)")
+        L.stsp_synth_launch.argtypes = [ctypes.POINTER(SynthDesc), vp]
+        L.stsp_synth_launch.restype = ci
+        L.stsp_synth_desc_size.argtypes = []
+        L.stsp_synth_desc_size.restype = ci
+        if L.stsp_synth_desc_size() != ctypes.sizeof(SynthDesc):
+            raise RuntimeError(f"SynthDesc: ctypes mirror is {ctypes.sizeof(SynthDesc)} bytes, "
+                               f"the library's {L.stsp_synth_desc_size()} (stale libstsp.so?)")
         _declare_runtime(L)
         _declare_tt(L)
         L.stsp_schedule_spin.argtypes = [ci]
