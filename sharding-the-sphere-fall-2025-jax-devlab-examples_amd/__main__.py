@@ -8,10 +8,14 @@
     schedule                                           print the reference 4-stage halo schedule
     roofline                                           slide-19 roofline / TT model for MI355X
     plot HISTORY.zarr FIELD OUTDIR [--log] [--products frames,band,six] [--every K] [--latlon NLAT NLON]
-                                    [--spectrum LMAX]
+                                    [--spectrum LMAX] [--tracks]
                                                        sphere frames, equatorial band, six-panel;
                                                        --latlon: regridded image + zonal-mean profile;
-                                                       --spectrum: log-log power per degree, first and last frame
+                                                       --spectrum: log-log power per degree, first and last frame;
+                                                       --tracks: history_particles.zarr (beside HISTORY.zarr)
+                                                       over the last frame's lat-lon image
+    sample HISTORY.zarr FIELD POINTS.npz OUT.npz       time series [frames, K] of a history field (or u, v) at
+                                                       the lat, lon (radians) of POINTS.npz, on the CPU
     regrid HISTORY.zarr FIELD NLAT NLON OUT.npz        regrid a history field (or u, v of a shallow-water
                                                        history) to the cell-centred lat-lon grid, on the CPU
     spectrum HISTORY.zarr FIELD LMAX OUT.npz           power per degree 0 .. LMAX of a history field (``ke``:
@@ -60,6 +64,13 @@ def main(argv=None):
                    help="also write the last frame regridded to NLAT x NLON with its zonal-mean profile")
     p.add_argument("--spectrum", type=int, metavar="LMAX", default=None,
                    help="also write the log-log power per degree 0 .. LMAX of the first and the last frame")
+    p.add_argument("--tracks", action="store_true",
+                   help="also draw the particle tracks of history_particles.zarr over the last frame")
+    sa = sub.add_parser("sample")
+    sa.add_argument("history")
+    sa.add_argument("field")
+    sa.add_argument("points")
+    sa.add_argument("out")
     rg = sub.add_parser("regrid")
     rg.add_argument("history")
     rg.add_argument("field")
@@ -121,6 +132,24 @@ def main(argv=None):
                                 title=f"{a.field}: power per degree",
                                 ylabel="E_l (m^2 / s^2)" if a.field == "ke" else "power per degree",
                                 labels=[f"day {r['time'][j] / 86400.0:.2f}" for j in k]))
+        if a.tracks:
+            import numpy as np
+            from .utils import zarr_lite
+            from .utils.viz import tracks_plot
+            ph = os.path.join(os.path.dirname(os.path.abspath(a.history)), "history_particles.zarr")
+            nlat, nlon = a.latlon or (91, 180)
+            r = regrid_history(a.history, a.field, nlat, nlon)
+            os.makedirs(a.outdir, exist_ok=True)
+            print(tracks_plot(r["field"][-1], r["lat"], r["lon"], zarr_lite.read_array(ph, "lat"),
+                              zarr_lite.read_array(ph, "lon"), os.path.join(a.outdir, f"{a.field}_tracks.png"),
+                              title=f"{a.field} and particle tracks, day {r['time'][-1] / 86400.0:.2f}"))
+        return 0
+    if a.cmd == "sample":
+        import numpy as np
+        pts = np.load(a.points)
+        r = sample_history(a.history, a.field, pts["lat"], pts["lon"])
+        np.savez(a.out, **r)
+        print(json.dumps({"out": a.out, "field": a.field, "shape": list(r["field"].shape)}))
         return 0
     if a.cmd == "spectrum":
         import numpy as np
@@ -197,6 +226,41 @@ def main(argv=None):
                     print(f)
             print(sphere_plot(g[0], s.grid, os.path.join(out, f"{s.fields[0]}_final.png"), log=log))
     return 0
+
+
+def sample_history(history: str, field: str, lat, lon) -> dict:
+    """Every frame of a history field at the points lat / lon [K] (radians;
+    ``u`` / ``v``: from the h, mx, my, mz of a shallow-water history), with the
+    twin on the CPU (models/points.py): field [frames, K], lat, lon, time."""
+    import numpy as np
+    import torch
+    from .models import points as mp
+    from .utils import zarr_lite
+    have = zarr_lite.list_arrays(history)
+    wind = field in ("u", "v") and field not in have
+    need = ["h", "mx", "my", "mz"] if wind else [field]
+    missing = [f for f in need if f not in have]
+    if missing:
+        raise ValueError(f"{history}: no array {missing} (it holds {[f for f in have if f not in ('time', 'step')]})")
+    lat = np.asarray(lat, dtype=np.float64).reshape(-1)
+    lon = np.asarray(lon, dtype=np.float64).reshape(-1)
+    p = mp.lonlat_points(lat, lon)
+    if len(p) < 1 or not np.isfinite(p).all():
+        raise ValueError("sample: lat and lon must be finite and hold at least one point")
+    src = np.stack([zarr_lite.read_array(history, f) for f in need], 1)       # [frames, C, 6, N, N]
+    loc = mp.locate(src.shape[-1], p)
+    if wind:
+        d = (np.stack([-np.sin(lon), np.cos(lon), np.zeros_like(lon)]) if field == "u" else
+             np.stack([-np.sin(lat) * np.cos(lon), -np.sin(lat) * np.sin(lon), np.cos(lat)]))
+        d = torch.as_tensor(d)
+    out = []
+    for fr in torch.as_tensor(np.ascontiguousarray(src, dtype=np.float64)):
+        if wind:
+            v = mp.velocity(fr, loc)
+            out.append((v[0] * d[0] + v[1] * d[1]) + v[2] * d[2])
+        else:
+            out.append(mp.sample(fr, loc)[0])
+    return {"field": torch.stack(out).numpy(), "lat": lat, "lon": lon, "time": zarr_lite.read_array(history, "time")}
 
 
 def regrid_history(history: str, field: str, nlat: int, nlon: int) -> dict:

@@ -45,7 +45,8 @@ from .parallel.layout import TileLayout
 from .parallel.mesh import setup_sharding
 from .utils import checkpoint as ckpt
 from .utils.config import Config, default_case, load_config
-from .utils.history import HistoryWriter, LatLonHistoryWriter, MetricsLogger, SpectraHistoryWriter
+from .utils.history import (HistoryWriter, LatLonHistoryWriter, MetricsLogger, ParticleHistoryWriter,
+                            SpectraHistoryWriter)
 
 
 # invariants the metrics records gain with the shallow-water model
@@ -260,6 +261,8 @@ class Solver:
                 path = ckpt.latest_checkpoint(self.checkpoint_root())
             if path:
                 self.restore_checkpoint(path)
+        if c.io.particles is not None:
+            self._init_particles(c.io.particles)
 
     # ---- pipeline stages: Geometry and Initial Conditions through zarr (PDF s.6) ----
     def _geometry_stage(self, N: int, radius: float) -> CubedSphereGrid:
@@ -451,6 +454,146 @@ class Solver:
         """[nlat] zonal mean of ``latlon_field(name, nlat, nlon)``."""
         r = self._latlon_arrays([name], nlat, nlon)
         return None if r is None else r[1][0].detach().cpu().numpy()
+
+    # ---- point sampling and particles (models/points.py, ops/points.py) ---------------
+    def _sum_terms(self, parts):
+        """The ranks' term arrays added: virtual ranks on the device in
+        ascending rank order, SPMD ranks by an all-reduce (one rank owns each
+        term, the others hold 0: exact in any order)."""
+        acc = parts[0]
+        for p in parts[1:]:
+            acc = acc + p
+        if self.mode == "spmd":
+            import torch.distributed as dist
+            acc = acc.contiguous()
+            if acc.is_cuda and dist.get_backend() == "gloo":
+                host = acc.cpu()
+                dist.all_reduce(host)
+                acc = host.to(acc.device)
+            else:
+                dist.all_reduce(acc)
+        return acc
+
+    def _sample_arrays(self, names, p: np.ndarray, lat: np.ndarray, lon: np.ndarray, der=None) -> torch.Tensor:
+        """[len(names), K] float64 of the current state at the unit vectors p
+        [K, 3] (lat, lon: the same points, for the winds), on every rank.
+        Several ranks sample the terms of their own cells, the arrays are added
+        (``_sum_terms``) and folded: the one-rank result bit for bit.
+        Collective under SPMD."""
+        from .models import points as mp
+        for name in names:
+            if name in DERIVED_FIELDS or name in LATLON_WINDS:
+                if self.physics.name != "swe":
+                    kind = "derived fields" if name in DERIVED_FIELDS else "winds"
+                    raise ValueError(f"{kind} are defined for the shallow-water model, not {self.physics.name!r}")
+            elif name not in self.fields:
+                raise ValueError(f"unknown sample field {name!r}; choose from {self.latlon_names()}")
+        sms = [e.points() for e in self.engines]
+        pts = [sm.points(p) for sm in sms]
+        terms = self.layout.num_ranks > 1
+        done = {}
+        if any(f in self.fields for f in names):
+            done["prog"] = [sm.fields(x, terms=terms) for sm, x in zip(sms, pts)]
+        if any(f in DERIVED_FIELDS for f in names):
+            der = self._derived_all() if der is None else der
+            done["der"] = [sm.tiles(x, f, terms=terms) for sm, x, (f, _) in zip(sms, pts, der)]
+        if any(f in LATLON_WINDS for f in names):
+            done["wind"] = [sm.velocity(x, terms=terms) for sm, x in zip(sms, pts)]
+        for kind, parts in done.items():
+            done[kind] = mp.fold_terms(self._sum_terms(parts)) if terms else parts[0]
+        if "wind" in done:
+            v = done["wind"]
+            t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=v.device)
+            e = t(np.stack([-np.sin(lon), np.cos(lon), np.zeros_like(lon)]))
+            n = t(np.stack([-np.sin(lat) * np.cos(lon), -np.sin(lat) * np.sin(lon), np.cos(lat)]))
+            done["wind"] = torch.stack([(v[0] * e[0] + v[1] * e[1]) + v[2] * e[2],
+                                        (v[0] * n[0] + v[1] * n[1]) + v[2] * n[2]])
+        rows = []
+        for name in names:
+            kind, k = (("prog", self.fields.index(name)) if name in self.fields else
+                       ("der", DERIVED_FIELDS.index(name)) if name in DERIVED_FIELDS else
+                       ("wind", LATLON_WINDS.index(name)))
+            rows.append(done[kind][k])
+        return torch.stack(rows)
+
+    def sample(self, names, lat, lon) -> Optional[np.ndarray]:
+        """[len(names), K] float64 of prognostic fields, ``vorticity``,
+        ``divergence``, ``pv``, ``u`` or ``v`` (the names ``latlon_field`` takes)
+        at the points ``lat`` / ``lon`` [K] (radians), on rank 0 (None
+        elsewhere).  Second order, dual-mesh interpolation (models/points.py)."""
+        from .models.points import lonlat_points
+        names = [names] if isinstance(names, str) else list(names)
+        lat = np.asarray(lat, dtype=np.float64).reshape(-1)
+        lon = np.asarray(lon, dtype=np.float64).reshape(-1)
+        p = lonlat_points(lat, lon)
+        if p.shape[0] < 1 or not np.isfinite(p).all():
+            raise ValueError("sample: lat and lon must be finite and hold at least one point")
+        r = self._sample_arrays(names, p, lat, lon)
+        return r.detach().cpu().numpy() if self.rank == 0 else None
+
+    def add_particles(self, lat, lon, interval: int = 1) -> None:
+        """Attach passive particles seeded at ``lat`` / ``lon`` [K] (radians),
+        advanced every ``interval`` steps by Heun's scheme in the tangent plane
+        (models/points.py).  Positions are replicated: every rank advances the
+        same particles from the summed velocity terms."""
+        if self.physics.name != "swe":
+            raise ValueError(f"particles are carried by the shallow-water model, not {self.physics.name!r}")
+        self._particles = [e.particles(lat, lon, interval) for e in self.engines]
+        self._pinterval = int(interval)
+        self._particles_stage(1)
+
+    def _init_particles(self, spec) -> None:
+        """Particles of the config block ``io.particles``."""
+        from .models.points import points_lonlat, random_points
+        if not isinstance(spec, dict) or not (("count" in spec) ^ ("lat" in spec and "lon" in spec)):
+            raise ValueError(f"io.particles: {{count, seed}} or {{lat, lon}} expected, not {spec!r}")
+        unknown = set(spec) - {"count", "seed", "lat", "lon", "interval", "fields"}
+        if unknown:
+            raise ValueError(f"io.particles: unknown key(s) {sorted(unknown)}")
+        if "count" in spec:
+            if not isinstance(spec["count"], int) or spec["count"] < 1:
+                raise ValueError(f"io.particles: count must be a positive integer, not {spec['count']!r}")
+            lat, lon = points_lonlat(random_points(spec["count"], int(spec.get("seed", 0))))
+        else:
+            lat, lon = np.asarray(spec["lat"], dtype=np.float64), np.asarray(spec["lon"], dtype=np.float64)
+        for f in spec.get("fields") or []:
+            if f not in self.latlon_names():
+                raise ValueError(f"io.particles: unknown field {f!r}; choose from {self.latlon_names()}")
+        self.add_particles(lat, lon, int(spec.get("interval", 1)))
+        self._restore_particles()
+
+    def _restore_particles(self) -> None:
+        """Positions of the checkpoint just restored, when it holds them for
+        as many particles as are attached."""
+        x = getattr(self, "_restored_particles", None)
+        ps = getattr(self, "_particles", None)
+        if x is None or not ps or x.shape != (ps[0].K, 3):
+            return
+        for P in ps:
+            P.set_positions(x)
+        self._particles_stage(1)
+
+    def _particles_stage(self, stage: int) -> None:
+        """Corrector (0) or predictor (1) of every replica: sample, add, apply."""
+        ps = self._particles
+        terms = self.layout.num_ranks > 1
+        parts = [P.sample(stage, terms=terms) for P in ps]
+        tot = self._sum_terms(parts) if terms else parts[0]
+        for P in ps:
+            P.apply(stage, tot)
+
+    def _particles_advance(self) -> None:
+        if self.layout.num_ranks == 1:
+            self._particles[0].advance()         # one fused launch
+        else:
+            self._particles_stage(0)
+            self._particles_stage(1)
+
+    def particle_positions(self):
+        """(lat, lon) [K] numpy, radians (NaN: a lost particle)."""
+        if not getattr(self, "_particles", None):
+            raise ValueError("no particles attached (add_particles)")
+        return self._particles[0].lonlat()
 
     # ---- spectra (models/spectra.py, ops/spectra.py) --------------------------------
     def spectrum_names(self) -> List[str]:
@@ -799,8 +942,21 @@ class Solver:
         self.xgmi = self.fused = self._ipc = None
 
     def step(self, nsteps: int = 1) -> None:
+        """Advance the model ``nsteps`` steps; with particles attached, in
+        pieces of their interval with a particle advance after each."""
         if nsteps <= 0:
             return
+        if not getattr(self, "_particles", None):
+            return self._step_model(nsteps)
+        iv = self._pinterval
+        if nsteps % iv:
+            raise ValueError(f"step({nsteps}): with particles attached the step count must be a multiple of "
+                             f"their interval {iv}")
+        for _ in range(nsteps // iv):
+            self._step_model(iv)
+            self._particles_advance()
+
+    def _step_model(self, nsteps: int) -> None:
         if self.mode == "virtual":
             self.cluster.step(nsteps)
         elif self._use_native():
@@ -859,6 +1015,9 @@ class Solver:
 
         iv = {"history": io.history_interval, "checkpoint": io.checkpoint_interval,
               "metrics": io.metrics_interval, "watchdog": c.runtime.watchdog_interval}
+        particles = getattr(self, "_particles", None)
+        if particles:                            # chunks end at particle times
+            iv["particles"] = self._pinterval
         iv = {k: v * SUB for k, v in iv.items() if v > 0}
         hist = None
         if "history" in iv:
@@ -889,6 +1048,13 @@ class Solver:
             hsp = SpectraHistoryWriter(os.path.join(out, "history_spectra.zarr"), snames, io.spectra, n_out,
                                        attrs={"config": self.config, "N": self.layout.N}) if self.rank == 0 else None
             self._spectra_hist = (hsp, list(hfields))
+        # (writer on rank 0, names) of the particle frames; None: no particles in a config block
+        self._particle_hist = None
+        if hist is not None and particles and io.particles is not None:
+            pfields = list(io.particles.get("fields") or [])
+            hpa = ParticleHistoryWriter(os.path.join(out, "history_particles.zarr"), pfields, particles[0].K, n_out,
+                                        attrs={"config": self.config, "N": self.layout.N}) if self.rank == 0 else None
+            self._particle_hist = (hpa, pfields)
         metrics = MetricsLogger(os.path.join(out, "metrics.jsonl") if "metrics" in iv else None,
                                 enabled=self.rank == 0)
         cells = 6 * self.layout.N ** 2
@@ -943,10 +1109,13 @@ class Solver:
             st = SUB >> level
             chunk = chunk_at(p, st)
             with ph("step"):
-                self.step(chunk)
+                self._step_model(chunk)
             done += chunk
             drain()
             p = pos()
+            if particles and p % iv["particles"] == 0:
+                with ph("particles"):
+                    self._particles_advance()
             due = {k for k, v in iv.items() if p % v == 0 or p >= end}
             ok, checked = True, False
             if "watchdog" in due:
@@ -979,6 +1148,10 @@ class Solver:
                     self.set_dt(dt_cur * 0.5)
                     if abs(self.dt * (1 << level) - dt0) > 1e-9 * dt0:
                         self.set_dt(dt0 / (1 << level))
+                    if particles:                # the particle times stay put: twice the steps between them
+                        for P in particles:
+                            P.interval = self._pinterval << level
+                        self._particles_stage(1)
                     continue
                 raise FloatingPointError(f"non-finite state detected at step {self.step_count}")
             if hist is not None and "history" in due and p % iv["history"] == 0:
@@ -1061,6 +1234,40 @@ class Solver:
             self._snapshot_latlon(*self._latlon_hist, k, pending, async_copy, der)
         if getattr(self, "_spectra_hist", None) is not None:
             self._snapshot_spectra(*self._spectra_hist, k, pending, async_copy, der)
+        if getattr(self, "_particle_hist", None) is not None:
+            self._snapshot_particles(*self._particle_hist, k, pending, async_copy, der)
+
+    def _snapshot_particles(self, hpa, names, k: int, pending: List[Any], async_copy: bool, der=None) -> None:
+        """Particle positions of history frame k and the fields sampled there
+        (``io.particles``): copied to pinned host memory on the stepping stream
+        and written by the host queue like the frame itself.  Collective under
+        SPMD when fields are sampled."""
+        from .models.points import points_lonlat
+        t, sc = self.time, self.step_count
+        x = self._particles[0].st.x.detach()
+        v = x
+        if names:
+            lat = lon = None
+            if any(f in LATLON_WINDS for f in names):
+                lat, lon = points_lonlat(x.cpu().numpy())
+            v = torch.cat([x.reshape(-1), self._sample_arrays(names, x, lat, lon, der=der).to(x.device).reshape(-1)])
+        if hpa is None:
+            return
+        ev = None
+        if async_copy and v.is_cuda:
+            h = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
+            h.copy_(v, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        else:
+            h = v.cpu().clone()
+        K = x.shape[0]
+
+        def work():
+            a = h.numpy().reshape(-1)
+            la, lo = points_lonlat(a[:3 * K].reshape(K, 3))
+            hpa.write_frame(k, np.concatenate([la[None], lo[None], a[3 * K:].reshape(-1, K)]), t, sc)
+        pending.append((ev, work))
 
     def _snapshot_spectra(self, hsp, names, k: int, pending: List[Any], async_copy: bool, der=None) -> None:
         """Power per degree of history frame k (``io.spectra``): computed on the
@@ -1244,11 +1451,19 @@ class Solver:
         ev = torch.cuda.Event()
         ev.record()
 
+        px = None
+        if getattr(self, "_particles", None):
+            xd = self._particles[0].st.x.detach()
+            px = torch.empty(xd.shape, dtype=xd.dtype, pin_memory=True)
+            px.copy_(xd, non_blocking=True)
+            ev.record()
+
         def work():
-            self._write_checkpoint(root, step, t, dt, [(tiles, h.double().numpy()) for tiles, h in snaps])
+            self._write_checkpoint(root, step, t, dt, [(tiles, h.double().numpy()) for tiles, h in snaps],
+                                   particles=None if px is None else px.numpy())
         pending.append((ev, work))
 
-    def _write_checkpoint(self, root: str, step: int, t: float, dt: float, parts) -> str:
+    def _write_checkpoint(self, root: str, step: int, t: float, dt: float, parts, particles=None) -> str:
         d = ckpt.step_dir(root, step)
         meta = {"step": step, "time": t, "dt": dt, "N": self.layout.N,
                 "tiles_per_edge": self.layout.t, "num_ranks": self.layout.num_ranks,
@@ -1258,6 +1473,8 @@ class Solver:
         ckpt.begin(root, step, meta, self.fields, self.layout.N, self.layout.n, np.float64)
         for tiles, arr in parts:
             ckpt.write_tiles(d, self.fields, tiles, self.layout.tile_origin, arr, self.layout.n)
+        if particles is not None:
+            np.save(os.path.join(d, "particles.npy"), particles)
         ckpt.commit(d)
         ckpt.prune(root, self.cfg.io.keep_checkpoints)
         return d
@@ -1284,6 +1501,8 @@ class Solver:
                              e.tiles_view().detach().cpu().double().numpy(), self.layout.n)
         self._barrier()
         if self.rank == 0:
+            if getattr(self, "_particles", None):
+                np.save(os.path.join(d, "particles.npy"), self._particles[0].st.x.detach().cpu().numpy())
             ckpt.commit(d)
             ckpt.prune(root, self.cfg.io.keep_checkpoints)
         self._barrier()
@@ -1303,5 +1522,8 @@ class Solver:
         if self.xgmi is not None:
             self.xgmi.prime()      # remote ghosts of the restored state (collective)
         self.set_dt(float(meta["dt"]))
+        pfile = os.path.join(path, "particles.npy")
+        self._restored_particles = np.load(pfile) if os.path.exists(pfile) else None
+        self._restore_particles()
         self._log(f"Restored {path} (step {meta['step']}, t = {meta['time'] / DAY:.4f} days, "
                   f"written by {meta['num_ranks']} rank(s), tiles_per_edge {meta['tiles_per_edge']})")

@@ -241,6 +241,20 @@ class Engine:
             self._latlon[key] = LatLon(self, lat, lon)
         return self._latlon[key]
 
+    def points(self):
+        """``ops.points.PointSampler`` of this engine, built on first use."""
+        if getattr(self, "_points", None) is None:
+            from .ops.points import PointSampler
+            self._points = PointSampler(self)
+        return self._points
+
+    def particles(self, lat, lon, interval: int = 1):
+        """``ops.points.Particles`` seeded at ``lat`` / ``lon`` [K] (radians),
+        advanced every ``interval`` steps (shallow water)."""
+        from .models.points import lonlat_points
+        from .ops.points import Particles
+        return Particles(self, lonlat_points(lat, lon), interval)
+
     def spectra(self, lmax: int):
         """``ops.spectra.Spectra`` of this engine up to degree ``lmax``, built
         on first use and cached per ``lmax``."""

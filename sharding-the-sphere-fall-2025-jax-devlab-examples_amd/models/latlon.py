@@ -212,6 +212,95 @@ def _element_weights(cells: np.ndarray, p: np.ndarray, ctr: np.ndarray):
     return w, ins
 
 
+def _best(cells, cand, p, ctr):
+    """Per point: weights, inside measure and index of the lowest candidate
+    that contains it (none does: the candidate nearest to containing it)."""
+    M, nc = cand.shape
+    w = np.zeros((M, 4))
+    ins = np.full(M, -np.inf)
+    el = np.zeros(M, dtype=np.int64)
+    found = np.zeros(M, dtype=bool)
+    order = np.sort(np.where(cand >= 0, cand, np.iinfo(np.int64).max), 1)
+    for c in range(nc):
+        e = order[:, c]
+        m = np.nonzero((e != np.iinfo(np.int64).max) & ~found)[0]
+        if c and m.size:
+            m = m[e[m] != order[m, c - 1]]
+        if not m.size:
+            continue
+        wc, ic = _element_weights(cells[e[m]], p[m], ctr)
+        better = ic > ins[m]
+        mb = m[better]
+        w[mb], ins[mb], el[mb] = wc[better], ic[better], e[m][better]
+        found[m[ic >= -CONTAIN_TOL]] = True
+    return w, ins, el
+
+
+def locate_points(N: int, p: np.ndarray, mesh: Optional[DualMesh] = None):
+    """(src [K, 4] global cell ids, w [K, 4] weights, elem [K] element ids,
+    margin [K]) of the unit vectors p [K, 3] on the C<N> dual mesh (see the
+    module docstring).  ``margin`` is the distance of the point from the border
+    of the element that holds it: min(tx, 1 - tx, ty, 1 - ty) in cell units for
+    an interior quad, the inside measure (``quad_weights`` / ``tri_weights``) for
+    an edge quad or a corner triangle."""
+    mesh = DualMesh(N) if mesh is None else mesh
+    K = len(p)
+    dn = p @ FACE_FRAMES[:, 0].T                               # [K, 6]
+    face = np.argmax(dn, 1)                                    # ties: the lowest panel
+    fr = FACE_FRAMES[face]
+    d = np.einsum("kc,kc->k", p, fr[:, 0])
+    da = 0.5 * math.pi / N
+    x = (np.arctan(np.einsum("kc,kc->k", p, fr[:, 1]) / d) + 0.25 * math.pi) / da - 0.5
+    y = (np.arctan(np.einsum("kc,kc->k", p, fr[:, 2]) / d) + 0.25 * math.pi) / da - 0.5
+    # a point within rounding of a dual grid line is on it: the tie rule decides
+    x = np.where(np.abs(x - np.round(x)) <= CONTAIN_TOL, np.round(x), x)
+    y = np.where(np.abs(y - np.round(y)) <= CONTAIN_TOL, np.round(y), y)
+    src = np.zeros((K, 4), dtype=np.int64)
+    w = np.zeros((K, 4))
+    elem = np.zeros(K, dtype=np.int64)
+    margin = np.zeros(K)
+    xlo, xhi, ylo, yhi = x < 0, x > N - 1, y < 0, y > N - 1
+    inner = ~(xlo | xhi | ylo | yhi)
+    # interior quads: bilinear in (alpha, beta); a point on a dual grid line goes to
+    # the lower quad (the lowest id)
+    k = np.nonzero(inner)[0]
+    i0 = np.clip(np.ceil(x[k]) - 1, 0, N - 2).astype(np.int64)
+    j0 = np.clip(np.ceil(y[k]) - 1, 0, N - 2).astype(np.int64)
+    tx, ty = x[k] - i0, y[k] - j0
+    c = (face[k] * N + j0) * N + i0
+    src[k] = np.stack([c, c + 1, c + N, c + N + 1], 1)
+    w[k] = np.stack([(1 - tx) * (1 - ty), tx * (1 - ty), (1 - tx) * ty, tx * ty], 1)
+    elem[k] = (face[k] * (N - 1) + j0) * (N - 1) + i0
+    margin[k] = np.minimum(np.minimum(tx, 1 - tx), np.minimum(ty, 1 - ty))
+    # border band: candidates are the edge quads next to the point on each side it
+    # is beyond, and the nearest corner triangle
+    k = np.nonzero(~inner)[0]
+    if k.size:
+        cells = mesh.element_cells()[mesh.nint:]
+        nq = len(mesh.equad)
+        f, xk, yk = face[k], x[k], y[k]
+        cand = np.full((k.size, 7), -1, dtype=np.int64)
+        jy = np.clip(np.floor(yk), 0, N - 2).astype(np.int64)
+        jx = np.clip(np.floor(xk), 0, N - 2).astype(np.int64)
+        xs = np.where(xhi[k], 1, 0)
+        ys = np.where(yhi[k], 3, 2)
+        bx, by = xlo[k] | xhi[k], ylo[k] | yhi[k]
+        for o in (-1, 0, 1):
+            cand[:, 1 + o] = np.where(bx, mesh.eid[f, xs, np.clip(jy + o, 0, N - 2)], -1)
+            cand[:, 4 + o] = np.where(by, mesh.eid[f, ys, np.clip(jx + o, 0, N - 2)], -1)
+        cand[:, 6] = nq + mesh.ctri[f, (xk > 0.5 * (N - 1)) * 1 + (yk > 0.5 * (N - 1)) * 2]
+        ctr = CubedSphereGrid(N).centers().reshape(-1, 3)
+        bw, bins, bel = _best(cells, cand, p[k], ctr)
+        if (bins < -1e-9).any():
+            raise RuntimeError("lat-lon tables: a target point lies in none of its neighbouring elements")
+        cc = cells[bel]
+        src[k] = np.where(cc >= 0, cc, cc[:, :1])
+        w[k] = bw
+        elem[k] = mesh.nint + bel
+        margin[k] = bins
+    return src, w, elem, margin
+
+
 class LatLonTables:
     """Sources and weights of a lat-lon target grid on C<N> (see the module
     docstring).  ``elem[K]`` is the id of the element that holds each point."""
@@ -239,83 +328,7 @@ class LatLonTables:
 
     # ---- location and weights ------------------------------------------------------
     def _locate(self) -> None:
-        N, p, mesh = self.N, self.p, self.mesh
-        K = self.K
-        dn = p @ FACE_FRAMES[:, 0].T                               # [K, 6]
-        face = np.argmax(dn, 1)                                    # ties: the lowest panel
-        fr = FACE_FRAMES[face]
-        d = np.einsum("kc,kc->k", p, fr[:, 0])
-        da = 0.5 * math.pi / N
-        x = (np.arctan(np.einsum("kc,kc->k", p, fr[:, 1]) / d) + 0.25 * math.pi) / da - 0.5
-        y = (np.arctan(np.einsum("kc,kc->k", p, fr[:, 2]) / d) + 0.25 * math.pi) / da - 0.5
-        # a point within rounding of a dual grid line is on it: the tie rule decides
-        x = np.where(np.abs(x - np.round(x)) <= CONTAIN_TOL, np.round(x), x)
-        y = np.where(np.abs(y - np.round(y)) <= CONTAIN_TOL, np.round(y), y)
-        src = np.zeros((K, 4), dtype=np.int64)
-        w = np.zeros((K, 4))
-        elem = np.zeros(K, dtype=np.int64)
-        xlo, xhi, ylo, yhi = x < 0, x > N - 1, y < 0, y > N - 1
-        inner = ~(xlo | xhi | ylo | yhi)
-        # interior quads: bilinear in (alpha, beta); a point on a dual grid line goes to
-        # the lower quad (the lowest id)
-        k = np.nonzero(inner)[0]
-        i0 = np.clip(np.ceil(x[k]) - 1, 0, N - 2).astype(np.int64)
-        j0 = np.clip(np.ceil(y[k]) - 1, 0, N - 2).astype(np.int64)
-        tx, ty = x[k] - i0, y[k] - j0
-        c = (face[k] * N + j0) * N + i0
-        src[k] = np.stack([c, c + 1, c + N, c + N + 1], 1)
-        w[k] = np.stack([(1 - tx) * (1 - ty), tx * (1 - ty), (1 - tx) * ty, tx * ty], 1)
-        elem[k] = (face[k] * (N - 1) + j0) * (N - 1) + i0
-        # border band: candidates are the edge quads next to the point on each side it
-        # is beyond, and the nearest corner triangle
-        k = np.nonzero(~inner)[0]
-        if k.size:
-            cells = mesh.element_cells()[mesh.nint:]
-            nq = len(mesh.equad)
-            f, xk, yk = face[k], x[k], y[k]
-            cand = np.full((k.size, 7), -1, dtype=np.int64)
-            jy = np.clip(np.floor(yk), 0, N - 2).astype(np.int64)
-            jx = np.clip(np.floor(xk), 0, N - 2).astype(np.int64)
-            xs = np.where(xhi[k], 1, 0)
-            ys = np.where(yhi[k], 3, 2)
-            bx, by = xlo[k] | xhi[k], ylo[k] | yhi[k]
-            for o in (-1, 0, 1):
-                cand[:, 1 + o] = np.where(bx, mesh.eid[f, xs, np.clip(jy + o, 0, N - 2)], -1)
-                cand[:, 4 + o] = np.where(by, mesh.eid[f, ys, np.clip(jx + o, 0, N - 2)], -1)
-            cand[:, 6] = nq + mesh.ctri[f, (xk > 0.5 * (N - 1)) * 1 + (yk > 0.5 * (N - 1)) * 2]
-            ctr = CubedSphereGrid(N).centers().reshape(-1, 3)
-            bw, bins, bel = self._best(cells, cand, p[k], ctr)
-            if (bins < -1e-9).any():
-                raise RuntimeError("lat-lon tables: a target point lies in none of its neighbouring elements")
-            cc = cells[bel]
-            src[k] = np.where(cc >= 0, cc, cc[:, :1])
-            w[k] = bw
-            elem[k] = mesh.nint + bel
-        self.src, self.w, self.elem = src, w, elem
-
-    @staticmethod
-    def _best(cells, cand, p, ctr):
-        """Per point: weights, inside measure and index of the lowest candidate
-        that contains it (none does: the candidate nearest to containing it)."""
-        M, nc = cand.shape
-        w = np.zeros((M, 4))
-        ins = np.full(M, -np.inf)
-        el = np.zeros(M, dtype=np.int64)
-        found = np.zeros(M, dtype=bool)
-        order = np.sort(np.where(cand >= 0, cand, np.iinfo(np.int64).max), 1)
-        for c in range(nc):
-            e = order[:, c]
-            m = np.nonzero((e != np.iinfo(np.int64).max) & ~found)[0]
-            if c and m.size:
-                m = m[e[m] != order[m, c - 1]]
-            if not m.size:
-                continue
-            wc, ic = _element_weights(cells[e[m]], p[m], ctr)
-            better = ic > ins[m]
-            mb = m[better]
-            w[mb], ins[mb], el[mb] = wc[better], ic[better], e[m][better]
-            found[m[ic >= -CONTAIN_TOL]] = True
-        return w, ins, el
+        self.src, self.w, self.elem, _ = locate_points(self.N, self.p, self.mesh)
 
     # ---- per-rank index tables -------------------------------------------------------
     def rank_index(self, layout: TileLayout, rank: int) -> Tuple[np.ndarray, np.ndarray]:

@@ -282,6 +282,41 @@ typedef struct SynthDesc {
 } SynthDesc;
 int stsp_synth_launch(const SynthDesc* d, hipStream_t stream);
 int stsp_synth_desc_size(void);
+// Point sampling and Lagrangian particles (points_kernel.hip, ops/points.py;
+// definitions and the twin in models/points.py): one thread per point locates
+// it on the dual mesh of the cell centres and gathers four source cells.
+// `mode` 0 samples at p; 1 applies the corrector (`stage` 0) or the predictor
+// (`stage` 1) move from a velocity sampled before; 2 is the fused advance of one
+// rank (sample at xs, corrector, sample at x, predictor in one thread).
+typedef struct PointsDesc {
+  const void* Q;          // source channels [C][cs], element type; velocity: h, then M (3)
+  const int* cmap;        // [6 N N] global cell id -> index inside a channel, -1 = not owned
+  const int* eid;         // [6][4][N-1] edge quad of panel, side, position: row of bcell
+  const int* bcell;       // [nb][4] cells of the border elements: 12 (N-1) edge quads, then 8
+                          // corner triangles (fourth slot -1)
+  const int* ctri;        // [6][4] corner triangle of panel, quadrant: 0 .. 7
+  const double* bctr;     // [nb][4][3] unit centres of the cells of bcell
+  const double* p;        // mode 0: [K][3] points
+  double* out;            // mode 0 out: [C][K], or the terms [C][4][K]
+  int* elem;              // mode 0 out, nullable: [K] element id (-1: lost)
+  const double* vel;      // mode 1 in: [3][K] velocity sampled at xs (stage 0) / x (stage 1), or terms [3][4][K]
+  double* x;              // [K][3] particle positions (modes 1, 2)
+  double* xs;             // [K][3] predicted positions
+  double* v0;             // [K][3] V(x)
+  long long cs;           // channel stride of Q in elements
+  long long lim;          // elements of a channel the map may address, <= cs
+  double da;              // pi / (2 N)
+  double radius;          // sphere radius (m)
+  double dtp;             // particle step (s)
+  int K, N;
+  int C;                  // channels (3 in velocity mode)
+  int velocity;           // mode 0: 1 = v = M / h per source cell
+  int terms;              // out / vel hold the unsummed terms
+  int mode, stage;
+  int pad_;
+} PointsDesc;
+int stsp_points_launch(int dtype, const PointsDesc* d, hipStream_t stream);
+int stsp_points_desc_size(void);
 // Direct xGMI halo build constant: ring slots.
 int stsp_xg_slots(void);
 }

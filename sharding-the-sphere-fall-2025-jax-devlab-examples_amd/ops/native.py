@@ -108,6 +108,20 @@ class LatLonDesc(ctypes.Structure):
     ]
 
 
+class PointsDesc(ctypes.Structure):
+    """Mirror of PointsDesc (stsp_kernels.h): point sampling and particles."""
+    _fields_ = [
+        ("Q", ctypes.c_void_p), ("cmap", ctypes.c_void_p), ("eid", ctypes.c_void_p), ("bcell", ctypes.c_void_p),
+        ("ctri", ctypes.c_void_p), ("bctr", ctypes.c_void_p), ("p", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("elem", ctypes.c_void_p), ("vel", ctypes.c_void_p), ("x", ctypes.c_void_p), ("xs", ctypes.c_void_p),
+        ("v0", ctypes.c_void_p),
+        ("cs", ctypes.c_longlong), ("lim", ctypes.c_longlong),
+        ("da", ctypes.c_double), ("radius", ctypes.c_double), ("dtp", ctypes.c_double),
+        ("K", ctypes.c_int), ("N", ctypes.c_int), ("C", ctypes.c_int), ("velocity", ctypes.c_int),
+        ("terms", ctypes.c_int), ("mode", ctypes.c_int), ("stage", ctypes.c_int), ("pad_", ctypes.c_int),
+    ]
+
+
 class SpectraDesc(ctypes.Structure):
     """Mirror of SpectraDesc (stsp_kernels.h): spherical-harmonic analysis."""
     _fields_ = [
@@ -187,6 +201,13 @@ def load(build_if_missing: bool = True):
         if L.stsp_latlon_desc_size() != ctypes.sizeof(LatLonDesc):
             raise RuntimeError(f"LatLonDesc: ctypes mirror is {ctypes.sizeof(LatLonDesc)} bytes, "
                                f"the library's {L.stsp_latlon_desc_size()} (stale libstsp.so?)")
+        L.stsp_points_launch.argtypes = [ci, ctypes.POINTER(PointsDesc), vp]
+        L.stsp_points_launch.restype = ci
+        L.stsp_points_desc_size.argtypes = []
+        L.stsp_points_desc_size.restype = ci
+        if L.stsp_points_desc_size() != ctypes.sizeof(PointsDesc):
+            raise RuntimeError(f"PointsDesc: ctypes mirror is {ctypes.sizeof(PointsDesc)} bytes, "
+                               f"the library's {L.stsp_points_desc_size()} (stale libstsp.so?)")
         L.stsp_spectra_launch.argtypes = [ci, ctypes.POINTER(SpectraDesc), vp]
         L.stsp_spectra_launch.restype = ci
         L.stsp_spectra_desc_size.argtypes = []

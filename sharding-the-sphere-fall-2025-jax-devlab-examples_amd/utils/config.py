@@ -84,6 +84,12 @@ class IOConfig:
     # spectrum of the shallow-water model) goes to history_spectra.zarr
     # (models/spectra.py); null = off
     spectra: Optional[int] = None
+    # passive particles of the shallow-water model (models/points.py):
+    # {count: K, seed: s} (uniform on the sphere) or {lat: [...], lon: [...]}
+    # (radians), optional interval (steps per particle advance, default 1) and
+    # fields (sampled at the particles); every history frame's positions go to
+    # history_particles.zarr; null = off
+    particles: Optional[Dict[str, Any]] = None
 
 
 @dataclass

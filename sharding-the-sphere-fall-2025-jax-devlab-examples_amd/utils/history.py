@@ -146,6 +146,39 @@ class SpectraHistoryWriter:
         zarr_lite.write_chunk(self.path, "step", (0,), self._steps, meta=self._meta["step"])
 
 
+class ParticleHistoryWriter:
+    """Particle positions of the history frames (``io.particles``):
+
+        history_particles.zarr/lat, lon   shape (n_out, K), radians (NaN: lost)
+        history_particles.zarr/<field>    shape (n_out, K): sampled at the particles
+        history_particles.zarr/time, step
+
+    written whole, frame by frame, by rank 0."""
+
+    def __init__(self, path: str, fields: List[str], K: int, n_out: int, attrs: Optional[Dict[str, Any]] = None):
+        self.path, self.fields, self.n_out, self.K = path, list(fields), n_out, K
+        self.names = ["lat", "lon"] + self.fields
+        zarr_lite.create_group(path, attrs=dict(attrs or {}, fields=self.fields, K=K))
+        for f in self.names:
+            zarr_lite.create_array(path, f, (n_out, K), np.float64, chunks=(1, K))
+        zarr_lite.create_array(path, "time", (n_out,), np.float64, chunks=(n_out,))
+        zarr_lite.create_array(path, "step", (n_out,), np.int64, chunks=(n_out,))
+        self._meta = {f: zarr_lite.array_meta(path, f) for f in self.names + ["time", "step"]}
+        self._times = np.zeros(n_out)
+        self._steps = np.zeros(n_out, dtype=np.int64)
+
+    def write_frame(self, k: int, values: np.ndarray, t: float, step: int) -> None:
+        """values [2 + len(fields), K] (lat, lon, fields) for history slot k."""
+        if k >= self.n_out:
+            return
+        for j, name in enumerate(self.names):
+            zarr_lite.write_chunk(self.path, name, (k, 0), values[j][None], meta=self._meta[name])
+        self._times[k] = t
+        self._steps[k] = step
+        zarr_lite.write_chunk(self.path, "time", (0,), self._times, meta=self._meta["time"])
+        zarr_lite.write_chunk(self.path, "step", (0,), self._steps, meta=self._meta["step"])
+
+
 def read_history(path: str, field: str) -> np.ndarray:
     return zarr_lite.read_array(path, field)
 

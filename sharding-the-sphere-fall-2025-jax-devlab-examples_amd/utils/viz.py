@@ -94,6 +94,32 @@ def latlon_image(arr: np.ndarray, lat: np.ndarray, lon: np.ndarray, path: str, t
     return path
 
 
+def tracks_plot(arr: np.ndarray, lat: np.ndarray, lon: np.ndarray, plat: np.ndarray, plon: np.ndarray, path: str,
+                title: str = "", cmap: str = "viridis") -> str:
+    """Particle tracks ``plat`` / ``plon`` [frames, K] (radians, NaN: lost) over
+    the image of a regridded [nlat, nlon] array; a track is cut where it
+    crosses the date line, a dot marks the last position."""
+    plt = _plt()
+    latd, lond = np.degrees(np.asarray(lat)), np.degrees(np.asarray(lon))
+    py, px = np.degrees(np.asarray(plat, dtype=np.float64)), np.degrees(np.asarray(plon, dtype=np.float64))
+    fig, ax = plt.subplots(figsize=(10, 4.2))
+    im = ax.pcolormesh(lond, latd, np.asarray(arr), cmap=cmap, shading="nearest")
+    if px.shape[0] > 1:
+        cut = np.abs(np.diff(px, axis=0)) > 180.0
+        px = np.where(np.concatenate([cut, np.zeros((1, px.shape[1]), dtype=bool)]), np.nan, px)
+    ax.plot(px, py, color="w", lw=0.6, alpha=0.8)
+    ax.plot(np.degrees(np.asarray(plon))[-1], py[-1], "k.", ms=2.5)
+    ax.set_xlim(0.0, 360.0)
+    ax.set_ylim(-90.0, 90.0)
+    ax.set_xlabel("longitude (deg E)")
+    ax.set_ylabel("latitude (deg)")
+    ax.set_title(title)
+    fig.colorbar(im, ax=ax, pad=0.02)
+    fig.savefig(path, dpi=110, bbox_inches="tight")
+    plt.close(fig)
+    return path
+
+
 def six_panel(initial: np.ndarray, final: np.ndarray, path: str, title: str = "Initial vs Final",
               cmap: str = "viridis") -> str:
     plt = _plt()
