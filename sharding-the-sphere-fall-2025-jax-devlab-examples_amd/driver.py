@@ -30,15 +30,14 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 import torch
 
-from .engine import Engine, GraphStepper, VirtualCluster, assemble_global
+from .diagnostics import LATLON_WINDS, SolverDiagnostics
+from .engine import Engine, VirtualCluster
 from .models.advection import Advection
 from .models.base import limiter_code
 from .models.derived import FIELDS as DERIVED_FIELDS, INVARIANTS
 from .models.diffusion import Diffusion
 from .models.geometry import DAY, EARTH_RADIUS, CubedSphereGrid
-from .models.spectra import check_lmax, ke_spectrum as spectra_ke, power as spectra_power
-from .models.spectra import (MAX_CHANNELS as spectra_max_channels, band_factors as spectra_band,
-                             helmholtz as spectra_helmholtz, scale_degrees as spectra_scale)
+from .models.spectra import check_lmax
 from .models.swe import ShallowWater
 from .parallel.comm import NativeBuffers, TorchDistTransport
 from .parallel.layout import TileLayout
@@ -51,8 +50,6 @@ from .utils.history import (HistoryWriter, LatLonHistoryWriter, MetricsLogger, P
 
 # invariants the metrics records gain with the shallow-water model
 METRIC_INVARIANTS = ("potential_enstrophy", "circulation", "max_courant")
-# zonal and meridional wind of the lat-lon output (shallow water)
-LATLON_WINDS = ("u", "v")
 
 
 def make_physics(pc) -> Any:
@@ -131,8 +128,30 @@ class _HostQueue:
         self._items = []
 
 
-class Solver:
+def stage(v, async_copy: bool):
+    """(event or None, host copy) of the tensor ``v``, or of a list of tensors
+    (one event, a list of copies).  ``async_copy`` and device tensors: the copy
+    goes to pinned host memory on the current stream without blocking and the
+    event, recorded after it, says when the host may read it.  Otherwise a
+    plain blocking copy (a CPU tensor is cloned) and no event."""
+    vs = list(v) if isinstance(v, (list, tuple)) else [v]
+    ev = None
+    if async_copy and all(x.is_cuda for x in vs):
+        hs = []
+        for x in vs:
+            hs.append(torch.empty(x.shape, dtype=x.dtype, pin_memory=True))
+            hs[-1].copy_(x, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+    else:
+        hs = [x.cpu() if x.is_cuda else x.clone() for x in vs]
+    return ev, (hs if isinstance(v, (list, tuple)) else hs[0])
+
+
+class Solver(SolverDiagnostics):
     def __init__(self, config=None, verbose: bool = True):
+        super().__init__()
+        self._wd_pending = None       # (event, pinned flags) of the deferred watchdog check in flight
         self.cfg: Config = load_config(config)
         self.config: Dict[str, Any] = self.cfg.to_dict()
         self.verbose = verbose
@@ -330,18 +349,7 @@ class Solver:
 
     def gather_global(self) -> Optional[np.ndarray]:
         """[F, 6, N, N] on rank 0 (None elsewhere)."""
-        F = len(self.fields)
-        vals = self.local_values()
-        if self.mode == "spmd":
-            import torch.distributed as dist
-            objs = [None] * self.world
-            dist.all_gather_object(objs, vals)
-            vals = {}
-            for o in objs:
-                vals.update(o)
-            if self.rank != 0:
-                return None
-        return np.stack([assemble_global(self.layout, {r: v[f] for r, v in vals.items()}) for f in range(F)])
+        return self._gather_tiles(self.local_values())
 
     def global_field(self, name_or_index=0) -> Optional[np.ndarray]:
         f = self.fields.index(name_or_index) if isinstance(name_or_index, str) else name_or_index
@@ -357,417 +365,6 @@ class Solver:
                          device=self.device if self.device.type == "cuda" else "cpu")
         dist.all_reduce(t, op={"sum": dist.ReduceOp.SUM, "min": dist.ReduceOp.MIN, "max": dist.ReduceOp.MAX}[op])
         return dict(zip(keys, t.tolist()))
-
-    # ---- derived fields (models/derived.py, ops/derived.py) -------------------------
-    def _derived_all(self):
-        """[(fields [3, T, n, n], inv [8])] of every engine of this process.
-        Ranks with remote ghosts exchange first: all engines start, then all
-        finish (the virtual cluster's lockstep)."""
-        if self.physics.name != "swe":
-            raise ValueError(f"derived fields are defined for the shallow-water model, not {self.physics.name!r}")
-        ds = [e.derived_fields for e in self.engines]
-        for d in ds:
-            d.start()
-        for d in ds:
-            d.finish()
-        return [d.compute() for d in ds]
-
-    def derived_field(self, name: str) -> Optional[np.ndarray]:
-        """[6, N, N] of ``vorticity``, ``divergence`` or ``pv`` on rank 0 (None
-        elsewhere), like ``global_field``."""
-        if name not in DERIVED_FIELDS:
-            raise ValueError(f"unknown derived field {name!r}; choose from {list(DERIVED_FIELDS)}")
-        k = DERIVED_FIELDS.index(name)
-        vals = {e.rank: f[k].detach().cpu().double().numpy() for e, (f, _) in zip(self.engines, self._derived_all())}
-        if self.mode == "spmd":
-            import torch.distributed as dist
-            objs = [None] * self.world
-            dist.all_gather_object(objs, vals)
-            vals = {}
-            for o in objs:
-                vals.update(o)
-            if self.rank != 0:
-                return None
-        return assemble_global(self.layout, vals)
-
-    # ---- lat-lon output (models/latlon.py, ops/latlon.py) ---------------------------
-    def latlon_names(self) -> List[str]:
-        """What ``latlon_field`` / ``zonal_mean`` accept for this model."""
-        swe = self.physics.name == "swe"
-        return list(self.fields) + (list(DERIVED_FIELDS) + list(LATLON_WINDS) if swe else [])
-
-    def _latlon_arrays(self, names, nlat: int, nlon: int, der=None):
-        """(arrays [len(names), nlat, nlon], zonal means [len(names), nlat]
-        float64) of the current state on rank 0, None elsewhere: tensors on the
-        device (single, virtual) or on the CPU (spmd).  Several ranks gather the
-        terms of their own cells, the arrays are added in ascending rank order
-        (virtual ranks on the device, SPMD ranks on rank 0 after an
-        ``all_gather_object``) and the finish step runs on the sum: the one-rank
-        result bit for bit.  ``der``: the engines' derived fields when the
-        caller has them already (``_derived_all()``).  Collective under SPMD."""
-        for name in names:
-            if name in DERIVED_FIELDS or name in LATLON_WINDS:
-                if self.physics.name != "swe":
-                    kind = "derived fields" if name in DERIVED_FIELDS else "winds"
-                    raise ValueError(f"{kind} are defined for the shallow-water model, not {self.physics.name!r}")
-            elif name not in self.fields:
-                raise ValueError(f"unknown lat-lon field {name!r}; choose from {self.latlon_names()}")
-        lls = [e.latlon(nlat=nlat, nlon=nlon) for e in self.engines]
-        groups = []
-        terms = self.layout.num_ranks > 1
-        if any(f in self.fields for f in names):
-            groups.append(("prog", [ll.partial_fields(terms=terms) for ll in lls], False))
-        if any(f in DERIVED_FIELDS for f in names):
-            der = self._derived_all() if der is None else der
-            groups.append(("der", [ll.partial_tiles(f, terms=terms) for ll, (f, _) in zip(lls, der)], False))
-        if any(f in LATLON_WINDS for f in names):
-            groups.append(("wind", [ll.partial_velocity(terms=terms) for ll in lls], True))
-        done = {}
-        for kind, parts, project in groups:
-            if self.mode == "spmd":
-                import torch.distributed as dist
-                objs = [None] * self.world
-                dist.all_gather_object(objs, (self.rank, parts[0].detach().cpu().numpy()))
-                if self.rank != 0:
-                    continue
-                parts = [torch.as_tensor(a) for _, a in sorted(objs, key=lambda o: o[0])]
-            done[kind] = lls[0].finish(lls[0].add_partials(parts).contiguous(), project=project)
-        if self.rank != 0:
-            return None
-        rows, zms = [], []
-        for name in names:
-            kind, k = (("prog", self.fields.index(name)) if name in self.fields else
-                       ("der", DERIVED_FIELDS.index(name)) if name in DERIVED_FIELDS else
-                       ("wind", LATLON_WINDS.index(name)))
-            rows.append(done[kind][0][k])
-            zms.append(done[kind][1][k])
-        return torch.stack(rows), torch.stack(zms)
-
-    def latlon_field(self, name: str, nlat: int, nlon: int) -> Optional[np.ndarray]:
-        """[nlat, nlon] of a prognostic field, ``vorticity``, ``divergence``,
-        ``pv``, ``u`` or ``v`` on the cell-centred lat-lon grid, on rank 0 (None
-        elsewhere), like ``global_field``."""
-        r = self._latlon_arrays([name], nlat, nlon)
-        return None if r is None else r[0][0].detach().cpu().double().numpy()
-
-    def zonal_mean(self, name: str, nlat: int, nlon: int) -> Optional[np.ndarray]:
-        """[nlat] zonal mean of ``latlon_field(name, nlat, nlon)``."""
-        r = self._latlon_arrays([name], nlat, nlon)
-        return None if r is None else r[1][0].detach().cpu().numpy()
-
-    # ---- point sampling and particles (models/points.py, ops/points.py) ---------------
-    def _sum_terms(self, parts):
-        """The ranks' term arrays added: virtual ranks on the device in
-        ascending rank order, SPMD ranks by an all-reduce (one rank owns each
-        term, the others hold 0: exact in any order)."""
-        acc = parts[0]
-        for p in parts[1:]:
-            acc = acc + p
-        if self.mode == "spmd":
-            import torch.distributed as dist
-            acc = acc.contiguous()
-            if acc.is_cuda and dist.get_backend() == "gloo":
-                host = acc.cpu()
-                dist.all_reduce(host)
-                acc = host.to(acc.device)
-            else:
-                dist.all_reduce(acc)
-        return acc
-
-    def _sample_arrays(self, names, p: np.ndarray, lat: np.ndarray, lon: np.ndarray, der=None) -> torch.Tensor:
-        """[len(names), K] float64 of the current state at the unit vectors p
-        [K, 3] (lat, lon: the same points, for the winds), on every rank.
-        Several ranks sample the terms of their own cells, the arrays are added
-        (``_sum_terms``) and folded: the one-rank result bit for bit.
-        Collective under SPMD."""
-        from .models import points as mp
-        for name in names:
-            if name in DERIVED_FIELDS or name in LATLON_WINDS:
-                if self.physics.name != "swe":
-                    kind = "derived fields" if name in DERIVED_FIELDS else "winds"
-                    raise ValueError(f"{kind} are defined for the shallow-water model, not {self.physics.name!r}")
-            elif name not in self.fields:
-                raise ValueError(f"unknown sample field {name!r}; choose from {self.latlon_names()}")
-        sms = [e.points() for e in self.engines]
-        pts = [sm.points(p) for sm in sms]
-        terms = self.layout.num_ranks > 1
-        done = {}
-        if any(f in self.fields for f in names):
-            done["prog"] = [sm.fields(x, terms=terms) for sm, x in zip(sms, pts)]
-        if any(f in DERIVED_FIELDS for f in names):
-            der = self._derived_all() if der is None else der
-            done["der"] = [sm.tiles(x, f, terms=terms) for sm, x, (f, _) in zip(sms, pts, der)]
-        if any(f in LATLON_WINDS for f in names):
-            done["wind"] = [sm.velocity(x, terms=terms) for sm, x in zip(sms, pts)]
-        for kind, parts in done.items():
-            done[kind] = mp.fold_terms(self._sum_terms(parts)) if terms else parts[0]
-        if "wind" in done:
-            v = done["wind"]
-            t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=v.device)
-            e = t(np.stack([-np.sin(lon), np.cos(lon), np.zeros_like(lon)]))
-            n = t(np.stack([-np.sin(lat) * np.cos(lon), -np.sin(lat) * np.sin(lon), np.cos(lat)]))
-            done["wind"] = torch.stack([(v[0] * e[0] + v[1] * e[1]) + v[2] * e[2],
-                                        (v[0] * n[0] + v[1] * n[1]) + v[2] * n[2]])
-        rows = []
-        for name in names:
-            kind, k = (("prog", self.fields.index(name)) if name in self.fields else
-                       ("der", DERIVED_FIELDS.index(name)) if name in DERIVED_FIELDS else
-                       ("wind", LATLON_WINDS.index(name)))
-            rows.append(done[kind][k])
-        return torch.stack(rows)
-
-    def sample(self, names, lat, lon) -> Optional[np.ndarray]:
-        """[len(names), K] float64 of prognostic fields, ``vorticity``,
-        ``divergence``, ``pv``, ``u`` or ``v`` (the names ``latlon_field`` takes)
-        at the points ``lat`` / ``lon`` [K] (radians), on rank 0 (None
-        elsewhere).  Second order, dual-mesh interpolation (models/points.py)."""
-        from .models.points import lonlat_points
-        names = [names] if isinstance(names, str) else list(names)
-        lat = np.asarray(lat, dtype=np.float64).reshape(-1)
-        lon = np.asarray(lon, dtype=np.float64).reshape(-1)
-        p = lonlat_points(lat, lon)
-        if p.shape[0] < 1 or not np.isfinite(p).all():
-            raise ValueError("sample: lat and lon must be finite and hold at least one point")
-        r = self._sample_arrays(names, p, lat, lon)
-        return r.detach().cpu().numpy() if self.rank == 0 else None
-
-    def add_particles(self, lat, lon, interval: int = 1) -> None:
-        """Attach passive particles seeded at ``lat`` / ``lon`` [K] (radians),
-        advanced every ``interval`` steps by Heun's scheme in the tangent plane
-        (models/points.py).  Positions are replicated: every rank advances the
-        same particles from the summed velocity terms."""
-        if self.physics.name != "swe":
-            raise ValueError(f"particles are carried by the shallow-water model, not {self.physics.name!r}")
-        self._particles = [e.particles(lat, lon, interval) for e in self.engines]
-        self._pinterval = int(interval)
-        self._particles_stage(1)
-
-    def _init_particles(self, spec) -> None:
-        """Particles of the config block ``io.particles``."""
-        from .models.points import points_lonlat, random_points
-        if not isinstance(spec, dict) or not (("count" in spec) ^ ("lat" in spec and "lon" in spec)):
-            raise ValueError(f"io.particles: {{count, seed}} or {{lat, lon}} expected, not {spec!r}")
-        unknown = set(spec) - {"count", "seed", "lat", "lon", "interval", "fields"}
-        if unknown:
-            raise ValueError(f"io.particles: unknown key(s) {sorted(unknown)}")
-        if "count" in spec:
-            if not isinstance(spec["count"], int) or spec["count"] < 1:
-                raise ValueError(f"io.particles: count must be a positive integer, not {spec['count']!r}")
-            lat, lon = points_lonlat(random_points(spec["count"], int(spec.get("seed", 0))))
-        else:
-            lat, lon = np.asarray(spec["lat"], dtype=np.float64), np.asarray(spec["lon"], dtype=np.float64)
-        for f in spec.get("fields") or []:
-            if f not in self.latlon_names():
-                raise ValueError(f"io.particles: unknown field {f!r}; choose from {self.latlon_names()}")
-        self.add_particles(lat, lon, int(spec.get("interval", 1)))
-        self._restore_particles()
-
-    def _restore_particles(self) -> None:
-        """Positions of the checkpoint just restored, when it holds them for
-        as many particles as are attached."""
-        x = getattr(self, "_restored_particles", None)
-        ps = getattr(self, "_particles", None)
-        if x is None or not ps or x.shape != (ps[0].K, 3):
-            return
-        for P in ps:
-            P.set_positions(x)
-        self._particles_stage(1)
-
-    def _particles_stage(self, stage: int) -> None:
-        """Corrector (0) or predictor (1) of every replica: sample, add, apply."""
-        ps = self._particles
-        terms = self.layout.num_ranks > 1
-        parts = [P.sample(stage, terms=terms) for P in ps]
-        tot = self._sum_terms(parts) if terms else parts[0]
-        for P in ps:
-            P.apply(stage, tot)
-
-    def _particles_advance(self) -> None:
-        if self.layout.num_ranks == 1:
-            self._particles[0].advance()         # one fused launch
-        else:
-            self._particles_stage(0)
-            self._particles_stage(1)
-
-    def particle_positions(self):
-        """(lat, lon) [K] numpy, radians (NaN: a lost particle)."""
-        if not getattr(self, "_particles", None):
-            raise ValueError("no particles attached (add_particles)")
-        return self._particles[0].lonlat()
-
-    # ---- spectra (models/spectra.py, ops/spectra.py) --------------------------------
-    def spectrum_names(self) -> List[str]:
-        """What ``sh_coefficients`` / ``spectrum`` accept for this model."""
-        return list(self.fields) + (list(DERIVED_FIELDS) if self.physics.name == "swe" else [])
-
-    def _spectra_coeffs(self, names, lmax: int, der=None):
-        """Coefficients [len(names), 2, L+1, L+1] float64 of the current state
-        on rank 0, None elsewhere: a tensor on the device (single, virtual) or
-        on the CPU (spmd).  Every rank analyses its own cells and the ranks'
-        arrays are added in ascending rank order (virtual ranks on the device,
-        SPMD ranks on rank 0 after an ``all_gather_object``).  ``der``: the
-        engines' derived fields when the caller has them already
-        (``_derived_all()``).  Collective under SPMD."""
-        for name in names:
-            if name in LATLON_WINDS:
-                raise ValueError(f"{name!r} is a vector component, not a scalar on the sphere: it has no "
-                                 f"spherical-harmonic spectrum; use ke_spectrum for the winds")
-            if name in DERIVED_FIELDS:
-                if self.physics.name != "swe":
-                    raise ValueError(f"derived fields are defined for the shallow-water model, "
-                                     f"not {self.physics.name!r}")
-            elif name not in self.fields:
-                raise ValueError(f"unknown spectrum field {name!r}; choose from {self.spectrum_names()}")
-        sps = [e.spectra(lmax) for e in self.engines]
-        groups = []
-        if any(f in self.fields for f in names):
-            groups.append(("prog", [sp.partial_fields() for sp in sps]))
-        if any(f in DERIVED_FIELDS for f in names):
-            der = self._derived_all() if der is None else der
-            groups.append(("der", [sp.partial_tiles(f) for sp, (f, _) in zip(sps, der)]))
-        done = {}
-        for kind, parts in groups:
-            if self.mode == "spmd":
-                import torch.distributed as dist
-                objs = [None] * self.world
-                dist.all_gather_object(objs, (self.rank, parts[0].detach().cpu().numpy()))
-                if self.rank != 0:
-                    continue
-                parts = [torch.as_tensor(a) for _, a in sorted(objs, key=lambda o: o[0])]
-            done[kind] = sps[0].add_partials(parts)
-        if self.rank != 0:
-            return None
-        return torch.stack([done["prog"][self.fields.index(f)] if f in self.fields
-                            else done["der"][DERIVED_FIELDS.index(f)] for f in names])
-
-    def sh_coefficients(self, name: str, lmax: int) -> Optional[np.ndarray]:
-        """[2, L+1, L+1] real spherical-harmonic coefficients (cos, sin; [l, m])
-        of a prognostic field, ``vorticity``, ``divergence`` or ``pv`` on rank 0
-        (None elsewhere)."""
-        r = self._spectra_coeffs([name], lmax)
-        return None if r is None else r[0].detach().cpu().numpy()
-
-    def spectrum(self, name: str, lmax: int) -> Optional[np.ndarray]:
-        """[L+1] power per degree of ``sh_coefficients(name, lmax)``."""
-        r = self._spectra_coeffs([name], lmax)
-        return None if r is None else spectra_power(r)[0].detach().cpu().numpy()
-
-    def _ke_spectrum(self, lmax: int, der=None):
-        if self.physics.name != "swe":
-            raise ValueError(f"the kinetic-energy spectrum is defined for the shallow-water model, "
-                             f"not {self.physics.name!r}")
-        r = self._spectra_coeffs(["vorticity", "divergence"], lmax, der=der)
-        return None if r is None else spectra_ke(r[0], r[1], self.grid.radius)
-
-    def ke_spectrum(self, lmax: int) -> Optional[np.ndarray]:
-        """[L+1] kinetic energy per degree (m^2 / s^2) from the vorticity and
-        the divergence, on rank 0 (None elsewhere)."""
-        r = self._ke_spectrum(lmax)
-        return None if r is None else r.detach().cpu().numpy()
-
-    # ---- synthesis: filters, psi and chi (models/spectra.py, ops/spectra.py) ---------------
-    def _synthesise(self, coeffs, lmax: int) -> Optional[np.ndarray]:
-        """[C, 6, N, N] float64 on rank 0 (None elsewhere) of the coefficients
-        [C, 2, L+1, L+1] that rank 0 holds (a tensor; ignored elsewhere).  Under
-        SPMD they are broadcast from rank 0; every rank synthesises its own
-        cells and the tiles are gathered as ``derived_field`` gathers them.
-        Collective under SPMD."""
-        sps = [e.spectra(lmax) for e in self.engines]
-        if self.mode == "spmd":
-            import torch.distributed as dist
-            box = [coeffs.detach().cpu().numpy() if self.rank == 0 else None]
-            dist.broadcast_object_list(box, src=0)
-            coeffs = torch.as_tensor(box[0])
-        C = coeffs.shape[0]
-        vals = {}
-        for e, sp in zip(self.engines, sps):
-            # at most 8 channels per launch
-            parts = [sp.synthesise(coeffs[k:k + spectra_max_channels].contiguous())
-                     for k in range(0, C, spectra_max_channels)]
-            vals[e.rank] = torch.cat(parts).detach().cpu().numpy()
-        if self.mode == "spmd":
-            import torch.distributed as dist
-            objs = [None] * self.world
-            dist.all_gather_object(objs, vals)
-            vals = {}
-            for o in objs:
-                vals.update(o)
-            if self.rank != 0:
-                return None
-        return np.stack([assemble_global(self.layout, {r: v[k] for r, v in vals.items()}) for k in range(C)])
-
-    def synthesise(self, coeffs) -> Optional[np.ndarray]:
-        """The band-limited field of given real spherical-harmonic coefficients
-        on the solver's own cells: [6, N, N] for ``coeffs`` [2, L+1, L+1] (cos,
-        sin; [l, m]), [C, 6, N, N] for [C, 2, L+1, L+1]; float64, on rank 0
-        (None elsewhere).  Every rank passes the same array.  Entries with
-        m > l and S_l0 are not read."""
-        co = torch.as_tensor(np.asarray(coeffs, dtype=np.float64))
-        one = co.dim() == 3
-        if one:
-            co = co[None]
-        if co.dim() != 4 or co.shape[0] < 1 or co.shape[1] != 2 or co.shape[2] != co.shape[3]:
-            raise ValueError(f"synthesise: coefficients [2, L+1, L+1] or [C, 2, L+1, L+1] expected, "
-                             f"not {tuple(np.shape(coeffs))}")
-        lmax = check_lmax(int(co.shape[2]) - 1, self.layout.N)
-        r = self._synthesise(co.to(self.engines[0].device), lmax)
-        return None if r is None else (r[0] if one else r)
-
-    def filtered_field(self, name: str, lmax: int, factors) -> Optional[np.ndarray]:
-        """[6, N, N] float64 on rank 0 (None elsewhere): the field ``name``
-        (anything in ``spectrum_names()``) analysed to degree ``lmax``, its
-        coefficients of degree l multiplied by ``factors[l]`` ([L+1]; see
-        ``band_factors`` / ``exp_factors`` in models/spectra.py) and synthesised
-        on the solver's cells."""
-        f = torch.as_tensor(np.asarray(factors, dtype=np.float64))
-        lmax = check_lmax(lmax, self.layout.N)
-        if f.shape != (lmax + 1,):
-            raise ValueError(f"filtered_field: factors [{lmax + 1}] expected, not {tuple(f.shape)}")
-        r = self._spectra_coeffs([name], lmax)
-        co = None if r is None else spectra_scale(r, f.to(r.device))
-        r = self._synthesise(co, lmax)
-        return None if r is None else r[0]
-
-    def band_field(self, name: str, lmax: int, lmin: int = 0, lcut: Optional[int] = None) -> Optional[np.ndarray]:
-        """``filtered_field`` with the degrees ``lmin .. lcut`` (default: up to
-        ``lmax``) kept and the others dropped: a low-, high- or band-pass view."""
-        lmax = check_lmax(lmax, self.layout.N)
-        return self.filtered_field(name, lmax, spectra_band(lmax, lmin, lcut))
-
-    def _psi_chi(self, lmax: int, which: int, what: str) -> Optional[np.ndarray]:
-        if self.physics.name != "swe":
-            raise ValueError(f"the {what} is defined for the shallow-water model, "
-                             f"not {self.physics.name!r}")
-        r = self._spectra_coeffs(["vorticity", "divergence"], lmax)
-        co = None if r is None else spectra_helmholtz(r[0], r[1], self.grid.radius)[which][None]
-        r = self._synthesise(co, check_lmax(lmax, self.layout.N))
-        return None if r is None else r[0]
-
-    def streamfunction(self, lmax: int) -> Optional[np.ndarray]:
-        """[6, N, N] streamfunction psi (m^2 / s), psi_lm = -R^2 zeta_lm / (l (l+1))
-        to degree ``lmax`` (v = k x grad psi + grad chi), on rank 0 (None
-        elsewhere)."""
-        return self._psi_chi(lmax, 0, "streamfunction")
-
-    def velocity_potential(self, lmax: int) -> Optional[np.ndarray]:
-        """[6, N, N] velocity potential chi (m^2 / s) from the divergence, like
-        ``streamfunction``."""
-        return self._psi_chi(lmax, 1, "velocity potential")
-
-    def invariants(self) -> Dict[str, float]:
-        """mass, energy, potential_enstrophy, circulation, abs_circulation
-        (sums over the sphere) and max_courant (maximum) of the current state."""
-        sums: Dict[str, float] = {}
-        cmax = 0.0
-        for _, inv in self._derived_all():
-            for k, v in zip(INVARIANTS, inv.tolist()):
-                if k == "max_courant":
-                    cmax = max(cmax, v)
-                else:
-                    sums[k] = sums[k] + v if k in sums else v
-        out = self._allreduce(sums)
-        out.update(self._allreduce({"max_courant": cmax}, op="max"))
-        return {k: out[k] for k in INVARIANTS}
 
     def diagnostics(self) -> Dict[str, float]:
         tot: Dict[str, float] = {}
@@ -946,7 +543,7 @@ class Solver:
         pieces of their interval with a particle advance after each."""
         if nsteps <= 0:
             return
-        if not getattr(self, "_particles", None):
+        if not self._particles:
             return self._step_model(nsteps)
         iv = self._pinterval
         if nsteps % iv:
@@ -1015,7 +612,7 @@ class Solver:
 
         iv = {"history": io.history_interval, "checkpoint": io.checkpoint_interval,
               "metrics": io.metrics_interval, "watchdog": c.runtime.watchdog_interval}
-        particles = getattr(self, "_particles", None)
+        particles = self._particles
         if particles:                            # chunks end at particle times
             iv["particles"] = self._pinterval
         iv = {k: v * SUB for k, v in iv.items() if v > 0}
@@ -1031,30 +628,30 @@ class Solver:
                               attrs={"config": self.config}, frame_chunks=self.mode != "spmd")
             self._barrier()
             hist = HistoryWriter(hpath, hfields, self.layout.N, self.layout.n, n_out, create=False)
+        # the frame outputs written beside every history frame, in this order: (producer(der) ->
+        # device tensor, None off rank 0; writer on rank 0, else None; host tensor -> the writer's array)
+        frames = []
+        if hist is not None:
+            wattrs = {"config": self.config, "N": self.layout.N}
+            as_f64 = lambda h: h.double().numpy()                       # noqa: E731
             if io.latlon is not None:
                 # the same frames on the lat-lon grid: the selected fields, or the
                 # prognostic ones plus the winds of the shallow-water model
                 lfields = list(hfields) if io.history_fields is not None else (
                     self.fields + (list(LATLON_WINDS) if self.physics.name == "swe" else []))
-                if self.rank == 0:
-                    hll = LatLonHistoryWriter(os.path.join(out, "history_latlon.zarr"), lfields, io.latlon[0],
-                                              io.latlon[1], n_out, attrs={"config": self.config, "N": self.layout.N})
-        # (writer on rank 0, names) of the lat-lon frames; None: io.latlon unset
-        self._latlon_hist = (hll if self.rank == 0 else None, lfields) if hist is not None and io.latlon else None
-        # (writer on rank 0, names) of the spectra frames; None: io.spectra unset
-        self._spectra_hist = None
-        if hist is not None and io.spectra is not None:
-            snames = list(hfields) + (["ke"] if self.physics.name == "swe" else [])
-            hsp = SpectraHistoryWriter(os.path.join(out, "history_spectra.zarr"), snames, io.spectra, n_out,
-                                       attrs={"config": self.config, "N": self.layout.N}) if self.rank == 0 else None
-            self._spectra_hist = (hsp, list(hfields))
-        # (writer on rank 0, names) of the particle frames; None: no particles in a config block
-        self._particle_hist = None
-        if hist is not None and particles and io.particles is not None:
-            pfields = list(io.particles.get("fields") or [])
-            hpa = ParticleHistoryWriter(os.path.join(out, "history_particles.zarr"), pfields, particles[0].K, n_out,
-                                        attrs={"config": self.config, "N": self.layout.N}) if self.rank == 0 else None
-            self._particle_hist = (hpa, pfields)
+                hll = LatLonHistoryWriter(os.path.join(out, "history_latlon.zarr"), lfields, io.latlon[0],
+                                          io.latlon[1], n_out, attrs=wattrs) if self.rank == 0 else None
+                frames.append((lambda der: self._latlon_frame(lfields, der), hll, as_f64))
+            if io.spectra is not None:
+                snames = list(hfields) + (["ke"] if self.physics.name == "swe" else [])
+                hsp = SpectraHistoryWriter(os.path.join(out, "history_spectra.zarr"), snames, io.spectra, n_out,
+                                           attrs=wattrs) if self.rank == 0 else None
+                frames.append((lambda der: self._spectra_frame(list(hfields), der), hsp, as_f64))
+            if particles and io.particles is not None:      # particles of a config block
+                pfields = list(io.particles.get("fields") or [])
+                hpa = ParticleHistoryWriter(os.path.join(out, "history_particles.zarr"), pfields, particles[0].K,
+                                            n_out, attrs=wattrs) if self.rank == 0 else None
+                frames.append((lambda der: self._particles_frame(pfields, der), hpa, self._particles_rows))
         metrics = MetricsLogger(os.path.join(out, "metrics.jsonl") if "metrics" in iv else None,
                                 enabled=self.rank == 0)
         cells = 6 * self.layout.N ** 2
@@ -1079,7 +676,7 @@ class Solver:
                     and self.step_count not in ckpt.list_checkpoints(self.checkpoint_root())):
                 self.save_checkpoint()      # the watchdog can always roll back to the run's start
             if hist is not None:
-                self._snapshot_history(hist, 0, pending, async_copy=False)
+                self._snapshot_history(hist, frames, 0, pending, async_copy=False)
                 drain(block=True)
             if self._use_native() and nsteps > 0:
                 lens, p, it = [], 0, 0
@@ -1156,7 +753,7 @@ class Solver:
                 raise FloatingPointError(f"non-finite state detected at step {self.step_count}")
             if hist is not None and "history" in due and p % iv["history"] == 0:
                 with ph("history"):
-                    self._snapshot_history(hist, p // iv["history"], pending, async_copy=deferred)
+                    self._snapshot_history(hist, frames, p // iv["history"], pending, async_copy=deferred)
             if "checkpoint" in due and p % iv["checkpoint"] == 0:
                 with ph("checkpoint"):
                     if deferred:
@@ -1196,30 +793,27 @@ class Solver:
         return summary
 
     # ---- run-loop helpers ----------------------------------------------------------
-    def _snapshot_history(self, hist: HistoryWriter, k: int, pending: List[Any], async_copy: bool) -> None:
+    def _snapshot_history(self, hist: HistoryWriter, frames, k: int, pending: "_HostQueue",
+                          async_copy: bool) -> None:
         """History frame k: the interior values are copied to host memory on
         the stepping stream; the zarr chunks are written when the copy is done
-        (``pending``), i.e. while the next chunk steps."""
+        (``pending``), i.e. while the next chunk steps.  The frame outputs
+        ``frames`` (``run``: lat-lon, spectra, particles) follow the same way:
+        computed on the stepping stream, staged, written by the host queue.
+        Collective under SPMD."""
         t, sc = self.time, self.step_count
-        snaps = []
         sel = self.cfg.io.history_fields
         # selected fields: the derived ones are computed here, on the stepping stream
         der = self._derived_all() if sel is not None and any(f in DERIVED_FIELDS for f in sel) else None
+        vals = []
         for j, e in enumerate(self.engines):
             v = e.tiles_view().detach()
             if sel is not None:
                 v = torch.stack([der[j][0][DERIVED_FIELDS.index(f)] if f in DERIVED_FIELDS
                                  else v[self.fields.index(f)] for f in sel])
-            if async_copy:
-                h = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
-                h.copy_(v, non_blocking=True)
-            else:
-                h = v.cpu()
-            snaps.append((e.plan.tiles, h))
-        ev = None
-        if async_copy:
-            ev = torch.cuda.Event()
-            ev.record()
+            vals.append(v)
+        ev, hs = stage(vals, async_copy)
+        snaps = [(e.plan.tiles, h) for e, h in zip(self.engines, hs)]
 
         def work():
             parts = [(list(tiles), h.double().numpy()) for tiles, h in snaps]
@@ -1230,97 +824,12 @@ class Solver:
             if self.rank == 0:
                 hist.write_time(k, t, sc)
         pending.append((ev, work))
-        if getattr(self, "_latlon_hist", None) is not None:
-            self._snapshot_latlon(*self._latlon_hist, k, pending, async_copy, der)
-        if getattr(self, "_spectra_hist", None) is not None:
-            self._snapshot_spectra(*self._spectra_hist, k, pending, async_copy, der)
-        if getattr(self, "_particle_hist", None) is not None:
-            self._snapshot_particles(*self._particle_hist, k, pending, async_copy, der)
-
-    def _snapshot_particles(self, hpa, names, k: int, pending: List[Any], async_copy: bool, der=None) -> None:
-        """Particle positions of history frame k and the fields sampled there
-        (``io.particles``): copied to pinned host memory on the stepping stream
-        and written by the host queue like the frame itself.  Collective under
-        SPMD when fields are sampled."""
-        from .models.points import points_lonlat
-        t, sc = self.time, self.step_count
-        x = self._particles[0].st.x.detach()
-        v = x
-        if names:
-            lat = lon = None
-            if any(f in LATLON_WINDS for f in names):
-                lat, lon = points_lonlat(x.cpu().numpy())
-            v = torch.cat([x.reshape(-1), self._sample_arrays(names, x, lat, lon, der=der).to(x.device).reshape(-1)])
-        if hpa is None:
-            return
-        ev = None
-        if async_copy and v.is_cuda:
-            h = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
-            h.copy_(v, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-        else:
-            h = v.cpu().clone()
-        K = x.shape[0]
-
-        def work():
-            a = h.numpy().reshape(-1)
-            la, lo = points_lonlat(a[:3 * K].reshape(K, 3))
-            hpa.write_frame(k, np.concatenate([la[None], lo[None], a[3 * K:].reshape(-1, K)]), t, sc)
-        pending.append((ev, work))
-
-    def _snapshot_spectra(self, hsp, names, k: int, pending: List[Any], async_copy: bool, der=None) -> None:
-        """Power per degree of history frame k (``io.spectra``): computed on the
-        stepping stream, copied to pinned host memory there and written by the
-        host queue like the frame itself.  Collective under SPMD."""
-        t, sc = self.time, self.step_count
-        L = self.cfg.io.spectra
-        swe = self.physics.name == "swe"
-        if der is None and (swe or any(f in DERIVED_FIELDS for f in names)):
-            der = self._derived_all()
-        r = self._spectra_coeffs(names, L, der=der)
-        ke = self._ke_spectrum(L, der=der) if swe else None
-        if r is None:
-            return
-        v = spectra_power(r)
-        if ke is not None:
-            v = torch.cat([v, ke[None]])
-        v = v.detach()
-        ev = None
-        if async_copy and v.is_cuda:
-            h = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
-            h.copy_(v, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-        else:
-            h = v.cpu()
-
-        def work():
-            hsp.write_frame(k, h.double().numpy(), t, sc)
-        pending.append((ev, work))
-
-    def _snapshot_latlon(self, hll, names, k: int, pending: List[Any], async_copy: bool, der=None) -> None:
-        """Lat-lon arrays of history frame k (``io.latlon``): computed on the
-        stepping stream, copied to pinned host memory there and written by the
-        host queue like the frame itself.  Collective under SPMD."""
-        t, sc = self.time, self.step_count
-        nlat, nlon = self.cfg.io.latlon
-        r = self._latlon_arrays(names, nlat, nlon, der=der)
-        if r is None:
-            return
-        v = r[0].detach()
-        ev = None
-        if async_copy and v.is_cuda:
-            h = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
-            h.copy_(v, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-        else:
-            h = v.cpu()
-
-        def work():
-            hll.write_frame(k, h.double().numpy(), t, sc)
-        pending.append((ev, work))
+        for produce, writer, finish in frames:
+            v = produce(der)
+            if v is None or writer is None:
+                continue
+            ev, h = stage(v, async_copy)
+            pending.append((ev, lambda writer=writer, finish=finish, h=h: writer.write_frame(k, finish(h), t, sc)))
 
     def _snapshot_metrics(self, metrics: MetricsLogger, pending: List[Any], deferred: bool, cells: int,
                           done: int, wall0: float, p: int) -> None:
@@ -1345,11 +854,7 @@ class Solver:
                 for k in METRIC_INVARIANTS:
                     keys.append(k)
                     vals.append(inv[INVARIANTS.index(k)])
-        dev = torch.stack(vals)
-        h = torch.empty(dev.shape, dtype=dev.dtype, pin_memory=True)
-        h.copy_(dev, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
+        ev, h = stage(torch.stack(vals), True)
 
         def work():
             tot: Dict[str, float] = {}
@@ -1367,10 +872,7 @@ class Solver:
         flag = torch.stack([torch.isfinite(e.tiles_view()).all() for e in self.engines]).all()
         vals = [v.reshape(()).to(torch.float64) for e in self.engines
                 for v in e.physics.diagnostics(e.tiles_view(), e.tens).values()]
-        hf = torch.empty((), dtype=torch.bool, pin_memory=True)
-        hf.copy_(flag, non_blocking=True)
-        hv = torch.empty((len(vals),), dtype=torch.float64, pin_memory=True)
-        hv.copy_(torch.stack(vals), non_blocking=True)
+        stage([flag, torch.stack(vals)], True)
         if derived and self.physics.name == "swe":      # the derived-field kernels of the metrics records
             self._derived_all()
         torch.cuda.current_stream().synchronize()
@@ -1382,8 +884,7 @@ class Solver:
         one interval late; checkpoints drain the queue first, so a checkpoint
         never holds a state the watchdog has not passed)."""
         if not deferred:
-            prev = getattr(self, "_wd_pending", None)
-            self._wd_pending = None
+            prev, self._wd_pending = self._wd_pending, None
             ok = self.all_finite()
             if prev is not None:
                 ok = self._wd_result(prev) and ok
@@ -1395,12 +896,7 @@ class Solver:
         finite = torch.stack([torch.isfinite(e.tiles_view()).all() for e in self.engines]).all()
         errs = self.runner.err_words() if self.runner is not None else []
         clean = torch.stack([(w[0] == 0) for w in errs]).all() if errs else torch.ones_like(finite)
-        h = torch.empty(2, dtype=torch.bool, pin_memory=True)
-        h.copy_(torch.stack([finite, clean]), non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        prev = getattr(self, "_wd_pending", None)
-        self._wd_pending = (ev, h)
+        prev, self._wd_pending = self._wd_pending, stage(torch.stack([finite, clean]), True)
         if prev is None:
             return True
         return self._wd_result(prev)
@@ -1442,21 +938,12 @@ class Solver:
         once the copy is done (in order with the history frames before it)."""
         root = self.checkpoint_root()
         step, t, dt = self.step_count, self.time, self.dt
-        snaps = []
-        for e in self.engines:
-            v = e.tiles_view().detach()
-            h = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
-            h.copy_(v, non_blocking=True)
-            snaps.append((e.plan.tiles, h))
-        ev = torch.cuda.Event()
-        ev.record()
-
-        px = None
-        if getattr(self, "_particles", None):
-            xd = self._particles[0].st.x.detach()
-            px = torch.empty(xd.shape, dtype=xd.dtype, pin_memory=True)
-            px.copy_(xd, non_blocking=True)
-            ev.record()
+        vals = [e.tiles_view().detach() for e in self.engines]
+        if self._particles:
+            vals.append(self._particles[0].st.x.detach())
+        ev, hs = stage(vals, True)
+        snaps = [(e.plan.tiles, h) for e, h in zip(self.engines, hs)]
+        px = hs[-1] if self._particles else None
 
         def work():
             self._write_checkpoint(root, step, t, dt, [(tiles, h.double().numpy()) for tiles, h in snaps],
@@ -1501,7 +988,7 @@ class Solver:
                              e.tiles_view().detach().cpu().double().numpy(), self.layout.n)
         self._barrier()
         if self.rank == 0:
-            if getattr(self, "_particles", None):
+            if self._particles:
                 np.save(os.path.join(d, "particles.npy"), self._particles[0].st.x.detach().cpu().numpy())
             ckpt.commit(d)
             ckpt.prune(root, self.cfg.io.keep_checkpoints)

@@ -337,15 +337,8 @@ class LatLonTables:
         rank does not own the source."""
         if layout.N != self.N:
             raise ValueError(f"tables are for C{self.N}, the layout is C{layout.N}")
-        tid, i, j = layout.locate(self.src)
-        own = np.asarray(layout.owner)[tid] == rank
-        li = layout._local_arr[tid]
-        n = layout.n
-        pad = np.where(own, layout.local_flat(self.src), -1)
-        unp = np.where(own, (li * n + j) * n + i, -1)
-        lim = np.iinfo(np.int32).max
-        assert pad.max() < lim and unp.max() < lim
-        return pad.astype(np.int32), unp.astype(np.int32)
+        pad, unp = layout.cell_maps(rank)
+        return pad[self.src], unp[self.src]
 
 
 _TABLES: Dict[tuple, LatLonTables] = {}

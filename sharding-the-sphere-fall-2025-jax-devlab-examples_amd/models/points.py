@@ -114,18 +114,8 @@ class PointTables:
 
 
 def rank_maps(layout: TileLayout, rank: int) -> Tuple[np.ndarray, np.ndarray]:
-    """(padded [6 N N], unpadded [6 N N]) int32: the index of every global cell
-    in the rank's padded storage [T P P] and in its [T, n, n] tiles; -1 for a
-    cell the rank does not own."""
-    g = np.arange(6 * layout.N * layout.N, dtype=np.int64)
-    tid, i, j = layout.locate(g)
-    own = np.asarray(layout.owner)[tid] == rank
-    li = layout._local_arr[tid]
-    n = layout.n
-    pad = np.where(own, layout.local_flat(g), -1)
-    unp = np.where(own, (li * n + j) * n + i, -1)
-    assert max(pad.max(), unp.max()) < np.iinfo(np.int32).max
-    return pad.astype(np.int32), unp.astype(np.int32)
+    """The rank's cell maps (``TileLayout.cell_maps``)."""
+    return layout.cell_maps(rank)
 
 
 @dataclass
@@ -162,9 +152,7 @@ def locate(N: int, p, cmap: Optional[np.ndarray] = None, mesh: Optional[ml.DualM
 # sampling
 # ----------------------------------------------------------------------------
 
-def fold_terms(t: torch.Tensor) -> torch.Tensor:
-    """[C, 4, K] -> [C, K]: ((t0 + t1) + t2) + t3."""
-    return ((t[:, 0] + t[:, 1]) + t[:, 2]) + t[:, 3]
+fold_terms = ml.fold_terms      # [C, 4, K] -> [C, K]: ((t0 + t1) + t2) + t3
 
 
 def _lost(loc: Located) -> torch.Tensor:

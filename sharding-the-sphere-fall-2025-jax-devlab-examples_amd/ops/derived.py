@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from ..models import derived as md
+from .common import use_hip
 
 BLOCK = 16
 
@@ -36,7 +37,7 @@ class DerivedFields:
         self.omega2 = 2.0 * float(phys.omega)
         self.tabs = md.derived_tables(e.geo, e.dtype, e.device)
         self.order = md.face_order(e.geo, e.device)
-        self.hip = e.backend == "hip" and e.device.type == "cuda"
+        self.hip = use_hip(e)
         self._dist = None
         # remote ghosts: the buffer the exchange of transport() fills
         self.recv = self.transport().recv

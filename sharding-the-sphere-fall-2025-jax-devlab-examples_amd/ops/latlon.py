@@ -13,7 +13,7 @@ One rank:   ``fields(q)``, ``tiles(x)``, ``winds(q)`` -> (arrays, zonal means).
 Several:    every rank's ``partial_*(terms=True)``: dense, the four terms of
             every sum kept apart ([C, 4, K]), 0 where the rank does not own the
             source; the ranks' arrays added in ascending rank order
-            (``add_partials``: exact, one rank owns each term), then ``finish`` on
+            (``ops.common.add_partials``: exact, one rank owns each term), then ``finish`` on
             the sum, which folds the terms in the one-rank association.
 
 All shape contracts the kernel relies on are checked here, on the host, before
@@ -21,14 +21,13 @@ anything is launched.
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence, Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
 from ..models import latlon as ml
-
-MAX_K = (1 << 31) - 256           # k and the workgroup count stay in int
+from .common import MAX_K, assert_interior, use_hip
 
 
 class LatLon:
@@ -43,7 +42,7 @@ class LatLon:
                                    self.nlat, self.nlon)
         self.S = plan.S
         self.cells = plan.T * plan.n * plan.n
-        self.hip = e.backend == "hip" and e.device.type == "cuda"
+        self.hip = use_hip(e)
         self._cpu = None          # tables on the CPU, for a finish step on gathered partials (SPMD rank 0)
         # ---- host-side shape contract checks ------------------------------------
         if self.K > MAX_K:
@@ -56,11 +55,7 @@ class LatLon:
             for v in (tb.east, tb.north):
                 assert v.dtype == torch.float64 and v.shape == (self.K, 3) and v.is_contiguous()
         # the padded table addresses interior cells only (a ghost slot is never a source)
-        if self.K:
-            P, g, n = plan.P, plan.ng, plan.n
-            i = self.pad.idx[self.pad.idx >= 0].long() % (P * P)
-            x, y = i % P, i // P
-            assert bool(((x >= g) & (x < g + n) & (y >= g) & (y < g + n)).all())
+        assert_interior(plan, pad)
         if self.hip:
             from . import native
             self.lib = native.require_native()
@@ -114,14 +109,6 @@ class LatLon:
             return self._gather(q, self.pad, self.S, True, terms)
         t = ml.velocity_terms(q[0], q[1:4], self.pad)
         return t if terms else ml.fold_terms(t)
-
-    @staticmethod
-    def add_partials(parts: Sequence[torch.Tensor]) -> torch.Tensor:
-        """The ranks' partials, given in ascending rank order, added in that order."""
-        acc = parts[0]
-        for p in parts[1:]:
-            acc = acc + p
-        return acc
 
     # ---- finish ---------------------------------------------------------------------------
     def finish(self, partial: torch.Tensor, project: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -147,6 +147,21 @@ class SynthDesc(ctypes.Structure):
     ]
 
 
+_VP, _CI, _P = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER
+# (launch symbol, its argtypes, descriptor class, size query: (symbol, arguments)) of every
+# descriptor: ``load`` declares both symbols and compares the library's size with the mirror's
+DESCRIPTORS = [
+    ("stsp_stage_launch", [_CI, _CI, _CI, _CI, _P(StageDesc), _VP], StageDesc, ("stsp_desc_size", (0,))),
+    ("stsp_fused_launch", [_CI, _P(FusedDesc), _VP], FusedDesc, ("stsp_desc_size", (1,))),
+    ("stsp_march3_launch", [_CI, _CI, _P(StageDesc), _P(March3Desc), _VP], March3Desc, ("stsp_desc_size", (3,))),
+    ("stsp_derived_launch", [_CI, _P(DerivedDesc), _VP], DerivedDesc, ("stsp_derived_desc_size", ())),
+    ("stsp_latlon_launch", [_CI, _P(LatLonDesc), _VP], LatLonDesc, ("stsp_latlon_desc_size", ())),
+    ("stsp_points_launch", [_CI, _P(PointsDesc), _VP], PointsDesc, ("stsp_points_desc_size", ())),
+    ("stsp_spectra_launch", [_CI, _P(SpectraDesc), _VP], SpectraDesc, ("stsp_spectra_desc_size", ())),
+    ("stsp_synth_launch", [_P(SynthDesc), _VP], SynthDesc, ("stsp_synth_desc_size", ())),
+]
+
+
 def lib_path() -> str:
     return _build.lib_for(os.environ.get("STSP_VARIANT", ""))
 
@@ -167,18 +182,12 @@ def load(build_if_missing: bool = True):
                     raise
         L = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
         vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-        L.stsp_stage_launch.argtypes = [ci, ci, ci, ci, ctypes.POINTER(StageDesc), vp]
-        L.stsp_stage_launch.restype = ci
         L.stsp_pack_launch.argtypes = [ci, vp, ci, ci, vp, ci, vp, vp]
         L.stsp_pack_launch.restype = ci
         L.stsp_copy_index_launch.argtypes = [ci, vp, vp, vp, vp, ci, ci, cl, cl, vp]
         L.stsp_copy_index_launch.restype = ci
         L.stsp_dpp_probe.argtypes = [vp, vp, vp, vp]
         L.stsp_dpp_probe.restype = ci
-        L.stsp_fused_launch.argtypes = [ci, ctypes.POINTER(FusedDesc), vp]
-        L.stsp_fused_launch.restype = ci
-        L.stsp_march3_launch.argtypes = [ci, ci, ctypes.POINTER(StageDesc), ctypes.POINTER(March3Desc), vp]
-        L.stsp_march3_launch.restype = ci
         L.stsp_fused_limits.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci)]
         L.stsp_fused_limits.restype = ci
         L.stsp_fused_tagh.argtypes = []
@@ -187,53 +196,19 @@ def load(build_if_missing: bool = True):
         L.stsp_fused_record_words.restype = ci
         L.stsp_fused_prime_launch.argtypes = [ci, vp, ci, vp, vp, ci, vp, ci, ci, vp]
         L.stsp_fused_prime_launch.restype = ci
-        L.stsp_derived_launch.argtypes = [ci, ctypes.POINTER(DerivedDesc), vp]
-        L.stsp_derived_launch.restype = ci
-        L.stsp_derived_desc_size.argtypes = []
-        L.stsp_derived_desc_size.restype = ci
-        if L.stsp_derived_desc_size() != ctypes.sizeof(DerivedDesc):
-            raise RuntimeError(f"DerivedDesc: ctypes mirror is {ctypes.sizeof(DerivedDesc)} bytes, "
-                               f"the library's {L.stsp_derived_desc_size()} (stale libstsp.so?)")
-        L.stsp_latlon_launch.argtypes = [ci, ctypes.POINTER(LatLonDesc), vp]
-        L.stsp_latlon_launch.restype = ci
-        L.stsp_latlon_desc_size.argtypes = []
-        L.stsp_latlon_desc_size.restype = ci
-        if L.stsp_latlon_desc_size() != ctypes.sizeof(LatLonDesc):
-            raise RuntimeError(f"LatLonDesc: ctypes mirror is {ctypes.sizeof(LatLonDesc)} bytes, "
-                               f"the library's {L.stsp_latlon_desc_size()} (stale libstsp.so?)")
-        L.stsp_points_launch.argtypes = [ci, ctypes.POINTER(PointsDesc), vp]
-        L.stsp_points_launch.restype = ci
-        L.stsp_points_desc_size.argtypes = []
-        L.stsp_points_desc_size.restype = ci
-        if L.stsp_points_desc_size() != ctypes.sizeof(PointsDesc):
-            raise RuntimeError(f"PointsDesc: ctypes mirror is {ctypes.sizeof(PointsDesc)} bytes, "
-                               f"the library's {L.stsp_points_desc_size()} (stale libstsp.so?)")
-        L.stsp_spectra_launch.argtypes = [ci, ctypes.POINTER(SpectraDesc), vp]
-        L.stsp_spectra_launch.restype = ci
-        L.stsp_spectra_desc_size.argtypes = []
-        L.stsp_spectra_desc_size.restype = ci
-        if L.stsp_spectra_desc_size() != ctypes.sizeof(SpectraDesc):
-            raise RuntimeError(f"SpectraDesc: ctypes mirror is {ctypes.sizeof(SpectraDesc)} bytes, "
-                               f"the library's {L.stsp_spectra_desc_size()} (stale libstsp.so?)")
-        L.stsp_synth_launch.argtypes = [ctypes.POINTER(SynthDesc), vp]
-        L.stsp_synth_launch.restype = ci
-        L.stsp_synth_desc_size.argtypes = []
-        L.stsp_synth_desc_size.restype = ci
-        if L.stsp_synth_desc_size() != ctypes.sizeof(SynthDesc):
-            raise RuntimeError(f"SynthDesc: ctypes mirror is {ctypes.sizeof(SynthDesc)} bytes, "
-                               f"the library's {L.stsp_synth_desc_size()} (stale libstsp.so?)")
+        for launch, argtypes, cls, (query, args) in DESCRIPTORS:
+            fn, size = getattr(L, launch), getattr(L, query)
+            fn.argtypes, fn.restype = argtypes, ci
+            size.argtypes, size.restype = [ci] * len(args), ci
+            if size(*args) != ctypes.sizeof(cls):
+                raise RuntimeError(f"{cls.__name__}: ctypes mirror is {ctypes.sizeof(cls)} bytes, "
+                                   f"the library's {size(*args)} (stale libstsp.so?)")
         _declare_runtime(L)
         _declare_tt(L)
         L.stsp_schedule_spin.argtypes = [ci]
         L.stsp_schedule_spin.restype = ci
         L.stsp_device_flags.argtypes = []
         L.stsp_device_flags.restype = ci
-        L.stsp_desc_size.argtypes = [ci]
-        L.stsp_desc_size.restype = ci
-        for k, cls in ((0, StageDesc), (1, FusedDesc), (3, March3Desc)):
-            if L.stsp_desc_size(k) != ctypes.sizeof(cls):
-                raise RuntimeError(f"{cls.__name__}: ctypes mirror is {ctypes.sizeof(cls)} bytes, "
-                                   f"the library's {L.stsp_desc_size(k)} (stale libstsp.so?)")
         _LIB = L
         return L
 

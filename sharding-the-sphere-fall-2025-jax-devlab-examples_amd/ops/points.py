@@ -28,8 +28,8 @@ import numpy as np
 import torch
 
 from ..models import points as mp
+from .common import MAX_K, assert_interior, use_hip
 
-MAX_K = (1 << 31) - 256           # k and the workgroup count stay in int
 CORRECTOR, PREDICTOR = 0, 1
 
 _TABLES: Dict[int, mp.PointTables] = {}
@@ -55,7 +55,7 @@ class PointSampler:
         self.S = plan.S
         self.cells = plan.T * plan.n * plan.n
         self.pad_np, self.unp_np = pad, unp
-        self.hip = e.backend == "hip" and e.device.type == "cuda"
+        self.hip = use_hip(e)
         # ---- host-side contract checks ------------------------------------------
         nb = 12 * (N - 1) + 8
         assert tab.eid.shape == (6, 4, N - 1) and tab.eid.min() >= 0 and tab.eid.max() < tab.nq == nb - 8
@@ -66,10 +66,7 @@ class PointSampler:
         for m, lim in ((pad, self.S), (unp, self.cells)):
             assert m.dtype == np.int32 and m.shape == (tab.ncell,) and m.min() >= -1 and m.max() < lim
         # the padded map addresses interior cells only (a ghost slot is never a source)
-        P, g, n = plan.P, plan.ng, plan.n
-        i = pad[pad >= 0].astype(np.int64) % (P * P)
-        x, y = i % P, i // P
-        assert bool(((x >= g) & (x < g + n) & (y >= g) & (y < g + n)).all())
+        assert_interior(plan, pad)
         if self.hip:
             from . import native
             self.lib = native.require_native()

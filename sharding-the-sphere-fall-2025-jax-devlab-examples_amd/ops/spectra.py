@@ -13,7 +13,7 @@ slot is ever read.
 One rank:   ``partial_fields(q)`` / ``partial_tiles(x)`` are the coefficients
             [C, 2, L+1, L+1] float64 (cos, sin; [l, m]).
 Several:    every rank's partial is the sum over its own cells; the ranks'
-            arrays are added in ascending rank order (``add_partials``).
+            arrays are added in ascending rank order (``ops.common.add_partials``).
 
 Synthesis:  ``synthesise(coeffs)`` is the band-limited field [C, T, n, n] float64
             of coefficients [C, 2, L+1, L+1] at this rank's cell centres: one
@@ -28,11 +28,12 @@ anything is launched.
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Sequence
+from typing import Optional
 
 import torch
 
 from ..models import spectra as ms
+from .common import assert_interior, use_hip
 
 BATCH = 128            # cells per batch of the kernel (its workgroup size)
 GROUP = 32             # degrees per group
@@ -49,7 +50,7 @@ class Spectra:
         pad, unp = ms.rank_index(plan)
         self.pad = torch.as_tensor(pad, device=e.device)
         self.unp = torch.as_tensor(unp, device=e.device)
-        self.hip = e.backend == "hip" and e.device.type == "cuda"
+        self.hip = use_hip(e)
         self._pack_index = None                     # synthesis: (l, m) of the packed rows, on the device
         self._abT = None                            # synthesis: the factors a, b as [m][l]
         self._bounds = {}                           # synthesis: chunks -> (host int array, device int32 tensor)
@@ -64,10 +65,7 @@ class Spectra:
             assert ix.dtype == torch.int32 and ix.shape == (self.cells,) and ix.is_contiguous()
             assert int(ix.min()) >= 0 and int(ix.max()) < lim
         # the padded table addresses interior cells only
-        P, g, n = plan.P, plan.ng, plan.n
-        i = self.pad.long() % (P * P)
-        x, y = i % P, i // P
-        assert bool(((x >= g) & (x < g + n) & (y >= g) & (y < g + n)).all())
+        assert_interior(plan, pad)
         if self.hip:
             from . import native
             self.lib = native.require_native()
@@ -184,14 +182,6 @@ class Spectra:
         d.cells, d.idx_limit, d.C, d.lmax, d.chunks = self.cells, self.cells, C, L, chunks
         native.check(self.lib.stsp_synth_launch(d, native.current_stream_handle(e.device)), "synthesis kernel")
         return out.reshape(C, plan.T, plan.n, plan.n)
-
-    @staticmethod
-    def add_partials(parts: Sequence[torch.Tensor]) -> torch.Tensor:
-        """The ranks' partials, given in ascending rank order, added in that order."""
-        acc = parts[0]
-        for p in parts[1:]:
-            acc = acc + p
-        return acc
 
     @staticmethod
     def power(coeffs: torch.Tensor) -> torch.Tensor:

@@ -225,6 +225,20 @@ class TileLayout:
         P, g = self.n + 2 * self.ng, self.ng
         return (li * P + j + g) * P + i + g
 
+    def cell_maps(self, rank: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(padded [6 N N], unpadded [6 N N]) int32: the index of every global cell
+        in the rank's padded storage [T P P] and in its [T, n, n] tiles; -1 for a
+        cell the rank does not own.  A table of global cell ids ``src`` becomes
+        the rank's index table as ``maps[src]`` (lat-lon sources, point sampling)."""
+        g = np.arange(6 * self.N * self.N, dtype=np.int64)
+        tid, i, j = self.locate(g)
+        own = self._owner_arr[tid] == rank
+        n = self.n
+        pad = np.where(own, self.local_flat(g), -1)
+        unp = np.where(own, (self._local_arr[tid] * n + j) * n + i, -1)
+        assert max(pad.max(), unp.max()) < np.iinfo(np.int32).max
+        return pad.astype(np.int32), unp.astype(np.int32)
+
     def tile_neighbors(self) -> np.ndarray:
         """[num_tiles, 4] tile across side W, E, S, N."""
         key = "tnbr"

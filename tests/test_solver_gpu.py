@@ -252,3 +252,43 @@ def test_solver_run_raises_when_a_fused_wait_times_out(tmp_path, monkeypatch):
     with pytest.raises(RuntimeError, match="did not finish its step in time"):
         s.run(nsteps=40)
     assert s.fused is not None and s.fused.timeout_ticks == 0
+
+
+def test_frame_outputs_together_equal_each_alone(tmp_path):
+    """Lat-lon, spectra and particle frames written beside the history frames
+    of one run (one shared set of derived fields per frame, one staging path,
+    the deferred pinned copies of the single-GPU mode) equal, array for array
+    and bit for bit, the frames of a run with only that product on; the last
+    lat-lon frame is ``latlon_field`` at the final state."""
+    from stsphere.utils import zarr_lite
+    products = {"latlon": [8, 16], "spectra": 4, "particles": {"count": 5, "fields": ["h", "u"]}}
+    groups = {"latlon": "history_latlon.zarr", "spectra": "history_spectra.zarr",
+              "particles": "history_particles.zarr"}
+
+    def run(name, **io):
+        c = _cfg(1, 2, N=12, out=str(tmp_path / name))
+        c["io"].update(history_interval=4, history_fields=["h", "vorticity"], **io)
+        s = Solver(c, verbose=False)
+        s.run(nsteps=8)
+        assert s.mode == "single" and s.runner is not None
+        return s
+
+    def arrays(name, group):
+        g = str(tmp_path / name / group)
+        return {a: zarr_lite.read_array(g, a) for a in zarr_lite.list_arrays(g)}
+
+    both = run("all", **products)
+    last = {f: both.latlon_field(f, 8, 16) for f in ("h", "vorticity")}
+    both.close()
+    for p, group in groups.items():
+        run(p, **{p: products[p]}).close()
+        for g in (group, "history.zarr"):
+            one, ref = arrays(p, g), arrays("all", g)
+            assert sorted(one) == sorted(ref) and len(one) > 2, (p, g)
+            for a in one:
+                assert one[a].shape[0] == 3 or a in ("lat", "lon", "degree"), (p, g, a)
+                assert np.array_equal(one[a], ref[a], equal_nan=True), (p, g, a)
+    ll = arrays("all", groups["latlon"])
+    assert list(ll["step"]) == [0, 4, 8]
+    for f, v in last.items():
+        assert np.array_equal(ll[f][-1], v), f
