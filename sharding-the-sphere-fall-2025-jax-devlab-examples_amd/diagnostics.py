@@ -5,8 +5,8 @@ sampling and particles, spherical-harmonic spectra and synthesis, invariants.
 solver's ``engines``, ``layout``, ``mode``, ``rank``, ``world``, ``fields``,
 ``physics`` and ``grid``.  Every product goes through the same three steps:
 
-* names      ``_resolve_names``: each name is a prognostic field, a derived
-             field or a wind, allowed or not for the model;
+* names      ``_resolve_names``: each name is a prognostic field, a tracer mixing
+             ratio, a derived field or a wind, allowed or not for the model;
 * sources    ``_source_groups``: per kind present, the partial of every
              engine of this process (``_derived_all()`` at most once);
 * combine    ``_gather_tiles`` (tiles to rank 0), ``_gather_partials`` (sum on
@@ -43,13 +43,50 @@ class SolverDiagnostics:
         self._restored_particles = None
 
     # ---- names, sources, rank combine -------------------------------------------------
+    def mix_names(self) -> List[str]:
+        """``q0 ..``: the mixing ratios hq_k / h of a shallow-water run with tracers."""
+        return [f"q{k}" for k in range(getattr(self.physics, "nq", 0))]
+
+    def _mixing_tiles(self, e) -> torch.Tensor:
+        """[NQ, T, n, n] mixing ratios of engine ``e`` (0 where h = 0)."""
+        qi = e.tiles_view().detach()
+        return torch.stack([self.physics.mixing_ratio(qi, k) for k in range(self.physics.nq)])
+
+    def tracer(self, k: int = 0) -> Optional[np.ndarray]:
+        """[6, N, N] mixing ratio q_k = hq_k / h of tracer ``k`` on rank 0 (None
+        elsewhere), like ``global_field``."""
+        nq = getattr(self.physics, "nq", 0)
+        if not 0 <= int(k) < nq:
+            raise ValueError(f"tracer({k}): this run carries {nq} tracer(s) (physics.tracers)")
+        return self._gather_tiles({e.rank: self._mixing_tiles(e)[int(k)].cpu().double().numpy()
+                                   for e in self.engines})
+
+    def tracer_extrema(self) -> Dict[str, List[float]]:
+        """{"tracer_min": [NQ], "tracer_max": [NQ]} of the mixing ratios over the
+        sphere, on every rank."""
+        nq = getattr(self.physics, "nq", 0)
+        lo, hi = {}, {}
+        for e in self.engines:
+            q = self._mixing_tiles(e).reshape(nq, -1)
+            for k in range(nq):
+                a, b = float(q[k].min()), float(q[k].max())
+                lo[f"{k}"] = min(lo.get(f"{k}", a), a)
+                hi[f"{k}"] = max(hi.get(f"{k}", b), b)
+        lo, hi = self._allreduce(lo, op="min"), self._allreduce(hi, op="max")
+        return {"tracer_min": [lo[f"{k}"] for k in range(nq)], "tracer_max": [hi[f"{k}"] for k in range(nq)]}
+
     def _resolve_names(self, names, what: str, winds: bool = True) -> List[Tuple[str, int]]:
         """[(kind, index)] of ``names``: ``prog`` (index into ``self.fields``),
-        ``der`` (into the derived fields) or ``wind`` (u, v).  ``what`` names the
-        product in the message for an unknown name; ``winds`` false: the product
-        is a scalar spectrum, which has no winds."""
+        ``mix`` (mixing ratio q_k of a tracer run), ``der`` (into the derived
+        fields) or ``wind`` (u, v).  ``what`` names the product in the message
+        for an unknown name; ``winds`` false: the product is a scalar spectrum,
+        which has no winds."""
         out = []
+        mix = self.mix_names()
         for name in names:
+            if name in mix:
+                out.append(("mix", mix.index(name)))
+                continue
             if name in LATLON_WINDS and not winds:
                 raise ValueError(f"{name!r} is a vector component, not a scalar on the sphere: it has no "
                                  f"spherical-harmonic spectrum; use ke_spectrum for the winds")
@@ -67,16 +104,18 @@ class SolverDiagnostics:
 
     def _source_groups(self, resolved, make, der=None) -> Dict[str, list]:
         """{kind: [make(kind, j, x) of engine j]} for every kind in ``resolved``
-        (prog, der, wind, in that order); x: the engine's derived fields [3, T,
-        n, n] for ``der``, else None.  ``der``: ``_derived_all()`` when the
+        (prog, mix, der, wind, in that order); x: the engine's derived fields [3,
+        T, n, n] for ``der``, its mixing ratios [NQ, T, n, n] for ``mix``, else None.  ``der``: ``_derived_all()`` when the
         caller has it already; it is computed here at most once."""
         out = {}
-        for kind in ("prog", "der", "wind"):
+        for kind in ("prog", "mix", "der", "wind"):
             if not any(k == kind for k, _ in resolved):
                 continue
             if kind == "der" and der is None:
                 der = self._derived_all()
-            out[kind] = [make(kind, j, der[j][0] if kind == "der" else None) for j in range(len(self.engines))]
+            out[kind] = [make(kind, j, der[j][0] if kind == "der" else
+                              self._mixing_tiles(e) if kind == "mix" else None)
+                         for j, e in enumerate(self.engines)]
         return out
 
     def _gather_tiles(self, vals: Dict[int, np.ndarray]) -> Optional[np.ndarray]:
@@ -153,7 +192,7 @@ class SolverDiagnostics:
     def latlon_names(self) -> List[str]:
         """What ``latlon_field`` / ``zonal_mean`` accept for this model."""
         swe = self.physics.name == "swe"
-        return list(self.fields) + (list(DERIVED_FIELDS) + list(LATLON_WINDS) if swe else [])
+        return list(self.fields) + self.mix_names() + (list(DERIVED_FIELDS) + list(LATLON_WINDS) if swe else [])
 
     def _latlon_arrays(self, names, nlat: int, nlon: int, der=None):
         """(arrays [len(names), nlat, nlon], zonal means [len(names), nlat]
@@ -169,7 +208,7 @@ class SolverDiagnostics:
 
         def make(kind, j, x):
             return (lls[j].partial_fields(terms=terms) if kind == "prog" else
-                    lls[j].partial_tiles(x, terms=terms) if kind == "der" else
+                    lls[j].partial_tiles(x, terms=terms) if kind in ("der", "mix") else
                     lls[j].partial_velocity(terms=terms))
         done = {}
         for kind, parts in self._source_groups(resolved, make, der).items():
@@ -212,7 +251,7 @@ class SolverDiagnostics:
 
         def make(kind, j, x):
             return (sms[j].fields(pts[j], terms=terms) if kind == "prog" else
-                    sms[j].tiles(pts[j], x, terms=terms) if kind == "der" else
+                    sms[j].tiles(pts[j], x, terms=terms) if kind in ("der", "mix") else
                     sms[j].velocity(pts[j], terms=terms))
         done = {kind: fold_terms(self._sum_terms(parts)) if terms else parts[0]
                 for kind, parts in self._source_groups(resolved, make, der).items()}
@@ -328,7 +367,7 @@ class SolverDiagnostics:
     # ---- spectra (models/spectra.py, ops/spectra.py) --------------------------------
     def spectrum_names(self) -> List[str]:
         """What ``sh_coefficients`` / ``spectrum`` accept for this model."""
-        return list(self.fields) + (list(DERIVED_FIELDS) if self.physics.name == "swe" else [])
+        return list(self.fields) + self.mix_names() + (list(DERIVED_FIELDS) if self.physics.name == "swe" else [])
 
     def _spectra_coeffs(self, names, lmax: int, der=None):
         """Coefficients [len(names), 2, L+1, L+1] float64 of the current state

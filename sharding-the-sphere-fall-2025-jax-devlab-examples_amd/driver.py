@@ -38,7 +38,7 @@ from .models.derived import FIELDS as DERIVED_FIELDS, INVARIANTS
 from .models.diffusion import Diffusion
 from .models.geometry import DAY, EARTH_RADIUS, CubedSphereGrid
 from .models.spectra import check_lmax
-from .models.swe import ShallowWater
+from .models.swe import MAX_TRACERS, ShallowWater, ShallowWaterTracers
 from .parallel.comm import NativeBuffers, TorchDistTransport
 from .parallel.layout import TileLayout
 from .parallel.mesh import setup_sharding
@@ -52,11 +52,32 @@ from .utils.history import (HistoryWriter, LatLonHistoryWriter, MetricsLogger, P
 METRIC_INVARIANTS = ("potential_enstrophy", "circulation", "max_courant")
 
 
+def _fold_tracers(rec: Dict[str, float], nq: int) -> Dict[str, Any]:
+    """The per-tracer scalars ``tracer_mass_k`` (and ``tracer_min_k`` /
+    ``tracer_max_k``) of a metrics record as lists ``tracer_mass`` (..) [NQ]."""
+    if not nq:
+        return rec
+    out = {k: v for k, v in rec.items() if not k.startswith("tracer_")}
+    for name in ("tracer_mass", "tracer_min", "tracer_max"):
+        if f"{name}_0" in rec:
+            out[name] = [rec[f"{name}_{k}"] for k in range(nq)]
+    return out
+
+
 def make_physics(pc) -> Any:
     model = pc.model.lower()
     case = pc.case or default_case(model)
     lim = limiter_code(pc.limiter)
+    tracers = pc.tracers
+    if tracers is not None and (not isinstance(tracers, (list, tuple)) or len(tracers) > MAX_TRACERS
+                                or not all(isinstance(t, str) for t in tracers)):
+        raise ValueError(f"physics.tracers: a list of at most {MAX_TRACERS} initial-condition names expected, "
+                         f"not {tracers!r}")
+    if tracers and model != "swe":
+        raise ValueError(f"physics.tracers: tracers are carried by the shallow-water model, not {model!r}")
     if model == "swe":
+        if tracers:
+            return ShallowWaterTracers(case, tracers=list(tracers), limiter=lim, alpha=pc.alpha)
         return ShallowWater(case, limiter=lim, alpha=pc.alpha)
     if model == "advection":
         return Advection(case, alpha=pc.alpha, limiter=lim)
@@ -219,6 +240,9 @@ class Solver(SolverDiagnostics):
         self.dtype = dtype
         N, t = c.grid.N, c.parallelization.tiles_per_edge
         phys0 = make_physics(c.physics)
+        if c.runtime.comm == "xgmi" and phys0.F not in (1, 4):
+            raise ValueError("runtime.comm = xgmi with physics.tracers: the direct xGMI exchange packs 1 or 4 "
+                             "fields; use comm: auto, ipc or rccl")
         # PPM reads three ghost layers: widen the halo if the config asks for fewer
         self.layout = TileLayout(N, t, nd, ng=max(c.grid.halo, phys0.halo), owner=self.sharding.owner)
         self.grid = self._geometry_stage(N, c.grid.radius or EARTH_RADIUS)
@@ -252,12 +276,13 @@ class Solver(SolverDiagnostics):
         self.fields = list(phys0.fields)
         hf = c.io.history_fields
         if hf is not None:
-            unknown = [f for f in hf if f not in self.fields and f not in DERIVED_FIELDS]
+            unknown = [f for f in hf if f not in self.fields and f not in DERIVED_FIELDS
+                       and f not in self.mix_names()]
             if not hf:
                 raise ValueError("io.history_fields: an empty list (use null for the prognostic fields)")
             if unknown:
                 raise ValueError(f"io.history_fields: unknown field(s) {unknown}; choose from "
-                                 f"{self.fields + list(DERIVED_FIELDS)}")
+                                 f"{self.fields + self.mix_names() + list(DERIVED_FIELDS)}")
             if phys0.name != "swe" and any(f in DERIVED_FIELDS for f in hf):
                 raise ValueError(f"io.history_fields: derived fields {list(DERIVED_FIELDS)} need the "
                                  f"shallow-water model, not {phys0.name!r}")
@@ -806,10 +831,13 @@ class Solver(SolverDiagnostics):
         # selected fields: the derived ones are computed here, on the stepping stream
         der = self._derived_all() if sel is not None and any(f in DERIVED_FIELDS for f in sel) else None
         vals = []
+        mix = self.mix_names()
         for j, e in enumerate(self.engines):
             v = e.tiles_view().detach()
             if sel is not None:
+                mq = self._mixing_tiles(e) if any(f in mix for f in sel) else None
                 v = torch.stack([der[j][0][DERIVED_FIELDS.index(f)] if f in DERIVED_FIELDS
+                                 else mq[mix.index(f)] if f in mix
                                  else v[self.fields.index(f)] for f in sel])
             vals.append(v)
         ev, hs = stage(vals, async_copy)
@@ -837,18 +865,26 @@ class Solver(SolverDiagnostics):
         wall = time.perf_counter() - wall0
         rec["cell_updates_per_s"] = cells * done / max(wall, 1e-12)
         swe = self.physics.name == "swe"
+        nq = getattr(self.physics, "nq", 0)
         if not deferred:
             extra = {}
             if swe:
                 inv = self.invariants()
                 extra = {k: inv[k] for k in METRIC_INVARIANTS}
-            metrics.log(**rec, **self.diagnostics(), **extra)
+            if nq:
+                extra.update(self.tracer_extrema())
+            metrics.log(**rec, **_fold_tracers(self.diagnostics(), nq), **extra)
             return
         keys, vals = [], []
         for e in self.engines:
             for k, v in e.physics.diagnostics(e.tiles_view(), e.tens).items():
                 keys.append(k)
                 vals.append(v.reshape(()).to(torch.float64))
+            if nq:      # extrema of the mixing ratios, through the same pinned copy
+                q = self._mixing_tiles(e).reshape(nq, -1).to(torch.float64)
+                for k in range(nq):
+                    keys += [f"tracer_min_{k}", f"tracer_max_{k}"]
+                    vals += [q[k].min(), q[k].max()]
         if swe:      # the one-launch reduction (ops/derived.py), through the same pinned copy
             for _, inv in self._derived_all():
                 for k in METRIC_INVARIANTS:
@@ -859,8 +895,13 @@ class Solver(SolverDiagnostics):
         def work():
             tot: Dict[str, float] = {}
             for k, v in zip(keys, h.tolist()):
-                tot[k] = max(tot[k], v) if k == "max_courant" and k in tot else tot.get(k, 0.0) + v
-            metrics.log(**rec, **tot)
+                if k in tot and (k == "max_courant" or k.startswith("tracer_max_")):
+                    tot[k] = max(tot[k], v)
+                elif k in tot and k.startswith("tracer_min_"):
+                    tot[k] = min(tot[k], v)
+                else:
+                    tot[k] = tot.get(k, 0.0) + v
+            metrics.log(**rec, **_fold_tracers(tot, nq))
         pending.append((ev, work))
 
     def _warm_checks(self, derived: bool = False) -> None:

@@ -11,6 +11,8 @@ invariant representation the reference exchanges across cube edges (PDF s.18
 * ``williamson_tc2``    steady geostrophic flow (analytic solution = IC).
 * ``williamson_tc5``    zonal flow over an isolated mountain.
 * ``williamson_tc6``    Rossby-Haurwitz wave, wavenumber 4.
+* ``tracer_field``      mixing ratios in [0, 1] for the shallow-water tracers:
+                        ``constant``, ``cosine_bell``, ``cap``, ``gradient``.
 * ``lima_flag``         checkerboard heat source on the top panel (face 0) on a
                         1 K background (PDF s.12 / s.17, log scale 1..1000 K).
 """
@@ -128,3 +130,36 @@ def gaussian_hill(p, center=(1.0, 0.0, 0.0), width=0.3, amp=1.0):
     c = c / np.linalg.norm(c)
     d2 = np.sum((p - c) ** 2, axis=-1)
     return amp * np.exp(-d2 / (width * width))
+
+
+# ---- shallow-water tracers (models/swe.py::ShallowWaterTracers) ------------------
+# centre (lon, lat) and angular radius of the ``cap`` tracer
+CAP_CENTER = (0.6, 0.3)
+CAP_RADIUS = 0.5
+TRACER_FIELDS = ("constant", "cosine_bell", "cap", "gradient")
+
+
+def tracer_field(name, p, radius=EARTH_RADIUS):
+    """Initial mixing ratio q in [0, 1] at unit positions p[..., 3]:
+
+    * ``constant``     q = 1 (stays 1: the tracer flux is the mass flux);
+    * ``cosine_bell``  the TC1 bell (270 E, 0 N, radius a/3) scaled to [0, 1];
+    * ``cap``          1 inside the spherical cap of angular radius ``CAP_RADIUS``
+                       about ``CAP_CENTER``, 0 outside (a discontinuity: the
+                       bounds test of the limiters);
+    * ``gradient``     (1 + sin lat) / 2.
+
+    A number instead of a name gives q = that number everywhere."""
+    if isinstance(name, (int, float)) and not isinstance(name, bool):
+        return np.full(p.shape[:-1], float(name))
+    if name == "constant":
+        return np.ones(p.shape[:-1])
+    if name == "cosine_bell":
+        return cosine_bell(p, h0=1.0, radius=radius)
+    if name == "cap":
+        lon_c, lat_c = CAP_CENTER
+        c = np.array([math.cos(lat_c) * math.cos(lon_c), math.cos(lat_c) * math.sin(lon_c), math.sin(lat_c)])
+        return (p @ c > math.cos(CAP_RADIUS)).astype(np.float64)
+    if name == "gradient":
+        return 0.5 * (1.0 + p[..., 2])
+    raise ValueError(f"unknown tracer initial condition {name!r}; choose from {list(TRACER_FIELDS)}")

@@ -24,7 +24,7 @@ from typing import Dict
 import numpy as np
 import torch
 
-from .base import Physics, RankGeometry, reconstruct, recon_halo
+from .base import PPM, Physics, RankGeometry, reconstruct, recon_halo
 from .geometry import GRAVITY, OMEGA, CubedSphereGrid
 from . import initial_conditions as ic
 
@@ -175,3 +175,86 @@ class ShallowWater(Physics):
         ke = 0.5 * (M * M).sum(0) / h
         pe = 0.5 * self.g * h * h + self.g * h * b
         return {"mass": (h * A).sum(), "energy": ((ke + pe) * A).sum()}
+
+
+MAX_TRACERS = 4
+
+
+class ShallowWaterTracers(ShallowWater):
+    """Shallow water carrying NQ passive tracers (1 <= NQ <= 4).
+
+    State (h, M, hq_0 .. hq_{NQ-1}) with hq_k = h q_k, tracer mass per unit
+    area.  The mixing ratios q_k = hq_k / h (0 where h = 0) are reconstructed
+    like h and v (same limiter, same panel-edge treatment) and ride the depth
+    flux of the same stage:  F_hq = F_h (F_h > 0 ? qL : qR).  Hence sum(hq A) is
+    conserved like the mass and q = const stays constant, which no scheme that
+    advects q with winds sampled from the SWE state can offer.  No source term,
+    no tangent projection.  The SWE rows are the parent's operations in the
+    parent's order: bit-identical to ``ShallowWater``.
+
+    ``tracers``: initial conditions, names of ``initial_conditions.tracer_field``
+    (or numbers: a constant mixing ratio).  PLR limiters only."""
+    kernel_id = 3
+
+    def __init__(self, case: str = "tc5", tracers=("cap",), **kw):
+        super().__init__(case, **kw)
+        tracers = list(tracers)
+        if not 1 <= len(tracers) <= MAX_TRACERS:
+            raise ValueError(f"shallow water with tracers: 1 to {MAX_TRACERS} tracers, got {len(tracers)}")
+        if self.limiter == PPM:
+            raise ValueError("shallow water with tracers: PPM (limiter 4) is not supported, the tracer "
+                             "stage kernel reconstructs with the PLR limiters 0 to 3 only")
+        for name in tracers:
+            if isinstance(name, str) and name not in ic.TRACER_FIELDS:
+                raise ValueError(f"unknown tracer initial condition {name!r}; choose from {list(ic.TRACER_FIELDS)}")
+        self.tracers = tracers
+        self.nq = len(tracers)
+        self.fields = ["h", "mx", "my", "mz"] + [f"hq{k}" for k in range(self.nq)]
+
+    def tracer_fields(self, grid: CubedSphereGrid) -> np.ndarray:
+        """Initial mixing ratios [NQ, 6, N, N]."""
+        p = grid.centers()
+        return np.stack([ic.tracer_field(name, p, radius=grid.radius) for name in self.tracers])
+
+    def initial_state(self, geo: RankGeometry) -> np.ndarray:
+        q4 = super().initial_state(geo)
+        q = self.tracer_fields(geo.grid)
+        return np.concatenate([q4] + [(q4[0] * geo.gather_global(q[k]))[None] for k in range(self.nq)], 0)
+
+    def kernel_params(self):
+        return dict(super().kernel_params(), nq=self.nq)
+
+    def rhs(self, qe, qi, tens, n, g):
+        h = qe[0]
+        safe = torch.where(h != 0, h, torch.ones_like(h))
+        w = torch.cat([h[None], qe[1:] / safe])                      # h, v, q_k (0 where h = 0)
+        (wL, wR, cL, cR), (yL, yR, dL, dR) = reconstruct(w, tens, g, n, self.limiter)
+        mx = tens["mx"].permute(1, 0, 2)[:, :, None, :]
+        Fx = self._flux(wL[:4], wR[:4], cL[:4], cR[:4], mx, tens["ex"])
+        my = tens["my"].permute(1, 0, 2)[:, :, :, None]
+        Gy = self._flux(yL[:4], yR[:4], dL[:4], dR[:4], my, tens["ey"])
+        Tx = Fx[0] * torch.where(Fx[0] > 0, wL[4:], wR[4:])          # upwind mixing ratio on the depth flux
+        Ty = Gy[0] * torch.where(Gy[0] > 0, yL[4:], yR[4:])
+        Fx = torch.cat([Fx, Tx])
+        Gy = torch.cat([Gy, Ty])
+        invA = tens["invA"]
+        dq = -((Fx[..., 1:] - Fx[..., :-1]) + (Gy[..., 1:, :] - Gy[..., :-1, :])) * invA
+        hc = qi[0]
+        M = qi[1:4]
+        r = tens["ctr"]
+        f = self.omega * 2.0 * r[2]
+        cor = torch.stack([r[1] * M[2] - r[2] * M[1], r[2] * M[0] - r[0] * M[2], r[0] * M[1] - r[1] * M[0]])
+        dq[1:4] += -f * cor + (hc * hc) * tens["sbal"] - self.g * hc * tens["gradb"]
+        return dq
+
+    def mixing_ratio(self, qi, k: int):
+        """q_k = hq_k / h of an interior state [F, ...] (0 where h = 0)."""
+        h = qi[0]
+        return torch.where(h != 0, qi[4 + k] / torch.where(h != 0, h, torch.ones_like(h)), torch.zeros_like(h))
+
+    def diagnostics(self, qi, tens):
+        d = super().diagnostics(qi, tens)
+        A = tens["area"]
+        for k in range(self.nq):
+            d[f"tracer_mass_{k}"] = (qi[4 + k] * A).sum()
+        return d

@@ -70,6 +70,8 @@ typedef struct StageDesc {
   const int* cgmap;     // [T][4][mg][mg] RankPlan.corner_map: remote slot -1 - m where < 0, else read as stored
   const int* cpush;     // [T][4][mg][mg] slot fed by the own cell of corner block (quad, a, b): >= 0 same
                         // rank, < -1 remote code (as push), -1 none (nullable)
+  int nq;               // shallow water with tracers (phys 3, swe_tracer_stage.hip): tracer fields, 1 .. 4;
+                        // the state then holds F = 4 + nq fields (h, M, hq_k) and recv is [R][4 + nq]
 } StageDesc;
 
 int stsp_stage_launch(int phys, int dtype, int bx, int by, const StageDesc* d, hipStream_t stream);

@@ -39,8 +39,12 @@ class DerivedFields:
         self.order = md.face_order(e.geo, e.device)
         self.hip = use_hip(e)
         self._dist = None
-        # remote ghosts: the buffer the exchange of transport() fills
-        self.recv = self.transport().recv
+        # remote ghosts: the buffer the exchange of transport() fills.  A state with
+        # more than the four SWE fields (tracers) exchanges all of them; the kernel
+        # and the twin read rows of four, so finish() copies the SWE columns over
+        self.F = int(phys.F)
+        self._recv_all = self.transport().recv
+        self.recv = self._recv_all if self.F == 4 else self._recv_all.new_zeros((plan.num_recv, 4))
         if self.hip:
             self._setup_kernel()
 
@@ -55,9 +59,9 @@ class DerivedFields:
         self.nblocks = T * nb * nb
         self.dcode = native.dtype_code(e.dtype)
         # ---- host-side shape contract checks --------------------------------
-        assert e.physics.F == 4
+        assert e.physics.F >= 4      # (h, M) first; tracer fields behind them are not read
         for b in e.pool:
-            assert b.shape == (4, S) and b.is_contiguous() and b.dtype == e.dtype
+            assert b.shape == (self.F, S) and b.is_contiguous() and b.dtype == e.dtype
         assert S == T * (n + 2 * mg) ** 2 and mg >= 1
         gm, cgm = plan.ghost_map, plan.corner_map
         assert e.gmap.dtype == torch.int32 and e.gmap.shape == (T, 4, mg, n)
@@ -119,7 +123,7 @@ class DerivedFields:
         if not isinstance(tr, NativeBuffers):
             return tr
         if self._dist is None:
-            self._dist = TorchDistTransport(self.e.plan, 4, self.e.dtype, self.e.device)
+            self._dist = TorchDistTransport(self.e.plan, self.e.physics.F, self.e.dtype, self.e.device)
         return self._dist
 
     def start(self, q: Optional[torch.Tensor] = None) -> None:
@@ -129,6 +133,8 @@ class DerivedFields:
     def finish(self) -> None:
         if self.e.plan.num_recv:
             self.transport().finish()
+            if self.F != 4:
+                self.recv.copy_(self._recv_all[:, :4])
 
     # ---- compute --------------------------------------------------------------------
     def compute(self, q: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -136,7 +142,7 @@ class DerivedFields:
         (default: the engine's state) as device tensors.  The HIP path returns
         its own buffers, overwritten by the next call."""
         e = self.e
-        q = e.state if q is None else q
+        q = (e.state if q is None else q)[:4]      # (h, M): a contiguous view of the leading rows
         if not self.hip:
             recv = self.recv if e.plan.num_recv else None
             return e.physics.derived(q, recv, e.gmap, e.cmap, e.tens, self.tabs, self.order, self.T, self.n,

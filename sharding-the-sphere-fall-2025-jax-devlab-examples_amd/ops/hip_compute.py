@@ -25,6 +25,9 @@ BLOCK_SHAPES = ((16, 16), (32, 8), (16, 8), (8, 16), (8, 8))
 # only through the direct xGMI exchange (XgmiHalo switches a rank to it,
 # rows 4), never through RCCL's receive buffer and block lists.
 MARCH_SHAPES = ((64, 4), (64, 8), (64, 16), (64, 32))
+# Shallow water with tracers (physics 3, ops/csrc/swe_tracer_stage.hip)
+TRACER_SHAPES = ((16, 16), (16, 8))
+SWE_KERNELS = (2, 3)      # physics ids that read the SWE geometry (mx, my, cgeo)
 
 
 MARCH_AUTO = (64, 4)
@@ -161,6 +164,18 @@ def choose_block(n: int, tiles: int = 0, cus: int = 0, limiter: int = 0, esize: 
     return best
 
 
+def choose_tracer_block(n: int, tiles: int = 0, cus: int = 0):
+    """Block shape of the tracer stage kernel, among ``TRACER_SHAPES`` by the
+    rule of ``choose_block``: 16 x 16 while its grid fits the compute units in
+    one pass and the 16 x 8 grid does not, else 16 x 8 (several blocks per CU:
+    five waves and half the LDS per block)."""
+    def count(bx, by):
+        return tiles * -(-n // bx) * -(-n // by)
+    if tiles and cus and count(16, 16) <= cus < count(16, 8):
+        return (16, 16)
+    return (16, 8)
+
+
 class HipCompute:
     def __init__(self, engine):
         e = engine
@@ -176,7 +191,10 @@ class HipCompute:
         self.march_wanted = False       # the size rule picks the streaming stage (XgmiHalo may switch)
         if e.block is None:
             cus = torch.cuda.get_device_properties(e.device).multi_processor_count
-            bx, by = choose_block(n, T, cus, getattr(phys, "limiter", 0), torch.tensor([], dtype=e.dtype).element_size())
+            if self.phys_id == 3:
+                bx, by = choose_tracer_block(n, T, cus)
+            else:
+                bx, by = choose_block(n, T, cus, getattr(phys, "limiter", 0), torch.tensor([], dtype=e.dtype).element_size())
             # streaming stage once the rank streams: measured C720 (3.1M cells, 12k per CU)
             # fp64 423 vs 467 us/step, fp32 190 vs 252 (64 x 4; 64 x 8: 431 / 203); C360 (3k per CU) a tie,
             # C180 the block kernel (43 vs 75): too few marches to hide their latency
@@ -194,6 +212,8 @@ class HipCompute:
                                  "a rank with remote ghosts marches 4 rows per wave through the xGMI exchange")
         elif (bx, by) not in BLOCK_SHAPES:
             raise ValueError(f"unsupported block shape {(bx, by)}")
+        elif self.phys_id == 3 and (bx, by) not in TRACER_SHAPES:
+            raise ValueError(f"shallow water with tracers runs blocks {TRACER_SHAPES}, not {(bx, by)}")
         self._shape(bx, by)
         # streaming stage geometry: compact (panel-shared tables, grad b from b) for fp64,
         # per-tile records for fp32 (C720 64x4: fp64 409 vs 415 us/step, fp32 225 vs 195,
@@ -225,9 +245,20 @@ class HipCompute:
             off = t["pe_base"][:, :, :kg].long() - torch.arange(n, device=t["pe_base"].device)
             assert int(off.min()) >= -ng_k and int(off.max()) <= ng_k - 1, \
                 "panel-edge interpolation pair outside the block window"
-        if self.phys_id == 2:
+        if self.phys_id in SWE_KERNELS:
             assert t["mx"].shape == (T, 3, n + 1) and t["my"].shape == (T, 3, n + 1)
             assert t["cgeo"].shape == (T, n, n, 8)
+        self._nq = 0
+        if self.phys_id == 3:      # (h, M, hq_k): the kernel strides the state and the receive buffer by 4 + nq
+            self._nq = int(phys.kernel_params()["nq"])
+            lim3 = int(phys.kernel_params().get("limiter", 0))
+            assert 1 <= self._nq <= 4 and F == 4 + self._nq, "tracer state: 4 SWE fields + 1 to 4 tracers"
+            assert 0 <= lim3 <= 3, "the tracer stage kernel has the PLR limiters 0 to 3"
+            assert plan.ng >= 2 and "pedge" in t and "pe_base" in t
+            self.lib.stsp_swe_tracer_lds.argtypes = [ctypes.c_int] * 4
+            self.lib.stsp_swe_tracer_lds.restype = ctypes.c_int
+            lds = int(self.lib.stsp_swe_tracer_lds(self.dcode, bx, by, self._nq))
+            assert 0 < lds <= 65536, f"tracer stage kernel: {lds} bytes of LDS per block"
         assert S == T * (n + 2 * plan.ng) ** 2
         pm = plan.push_map
         assert pm.shape == (T, 4, plan.ng, n) and pm.max(initial=-1) < S
@@ -319,8 +350,9 @@ class HipCompute:
         d.invA = p(t["invA"])
         d.ex = p(t["ex"])
         d.ey = p(t["ey"])
-        if self.phys_id == 2:
+        if self.phys_id in SWE_KERNELS:
             d.mx, d.my, d.cgeo = p(t["mx"]), p(t["my"]), p(t["cgeo"])
+        d.nq = self._nq
         if "pedge" in t:
             d.pedge = p(t["pedge"])
         if "pe_base" in t:

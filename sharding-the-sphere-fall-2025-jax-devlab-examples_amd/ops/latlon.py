@@ -103,8 +103,9 @@ class LatLon:
     def partial_velocity(self, q: Optional[torch.Tensor] = None, terms: bool = False) -> torch.Tensor:
         """The Cartesian velocity [3, K] of the padded shallow-water state."""
         q = self.e.state if q is None else q
-        if q.shape[0] != 4:
+        if q.shape[0] < 4:
             raise ValueError("winds need the shallow-water state (h, M)")
+        q = q[:4]      # (h, M): a contiguous view (tracer fields follow them)
         if self.hip:
             return self._gather(q, self.pad, self.S, True, terms)
         t = ml.velocity_terms(q[0], q[1:4], self.pad)

@@ -44,6 +44,8 @@ class StageDesc(ctypes.Structure):
         ("Nf", ctypes.c_int), ("frames", ctypes.c_int * 6),
         # carried tile-corner ghosts (parallel/layout.py::corner_sources)
         ("cgmap", ctypes.c_void_p), ("cpush", ctypes.c_void_p),
+        # shallow water with tracers (swe_tracer_stage.hip)
+        ("nq", ctypes.c_int),
     ]
 
 

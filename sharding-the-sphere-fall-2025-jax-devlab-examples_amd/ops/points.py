@@ -112,8 +112,10 @@ class PointSampler:
         from . import native
         p = self.points(p)
         K = p.shape[0]
-        if velocity and Q.shape[0] != 4:
+        if velocity and Q.shape[0] < 4:
             raise ValueError("the velocity needs the shallow-water state (h, M)")
+        if velocity:
+            Q = Q[:4]      # (h, M): a contiguous view (tracer fields follow them)
         C = 3 if velocity else Q.shape[0]
         if self.hip:
             out = torch.empty((C, 4, K) if terms else (C, K), dtype=torch.float64, device=self.e.device)
@@ -216,9 +218,9 @@ class Particles:
             return self.advance_sequenced(q)
         from . import native
         q = self.e.state if q is None else q
-        if q.shape[0] != 4:
+        if q.shape[0] < 4:
             raise ValueError("the velocity needs the shallow-water state (h, M)")
-        d = s._desc(q, True, self.K)
+        d = s._desc(q[:4], True, self.K)
         d.x, d.xs, d.v0 = native.ptr(self.st.x), native.ptr(self.st.xs), native.ptr(self.st.v0)
         d.C, d.velocity, d.mode = 3, 1, 2
         d.radius, d.dtp = self.radius, self.dtp

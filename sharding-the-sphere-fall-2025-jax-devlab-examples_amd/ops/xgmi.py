@@ -226,6 +226,11 @@ class XgmiHalo:
         refuse_if_forced()
         from .hip_compute import HipCompute
         e = engine
+        if e.physics.F not in (1, 4):
+            # the granule codecs pack 1 or 4 fields; raised before anything is
+            # allocated, so the solver's transport chain moves on to ipc / rccl
+            raise RuntimeError(f"the direct xGMI exchange packs 1 or 4 fields, not {e.physics.F} "
+                               f"(shallow water with tracers exchanges through ipc or rccl)")
         if not isinstance(e.compute, HipCompute):
             raise RuntimeError("XgmiHalo needs an Engine with backend='hip'")
         self.e = e

@@ -52,6 +52,10 @@ class PhysicsConfig:
     limiter: str = "mc"
     alpha: float = 0.0
     kappa: float = 2.0e6
+    # shallow water only: initial conditions of up to 4 passive tracers carried by
+    # the flow (models/initial_conditions.py::tracer_field: constant | cosine_bell |
+    # cap | gradient); null or empty = none
+    tracers: Optional[List[str]] = None
 
 
 @dataclass
