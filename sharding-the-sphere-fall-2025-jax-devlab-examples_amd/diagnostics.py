@@ -188,6 +188,36 @@ class SolverDiagnostics:
         return self._gather_tiles({e.rank: f[k].detach().cpu().double().numpy()
                                    for e, (f, _) in zip(self.engines, self._derived_all())})
 
+    # ---- Laplacian of a field (models/dissipation.py, ops/dissipation.py) --------------
+    def laplacian(self, name: str) -> Optional[np.ndarray]:
+        """[6, N, N] float64 of the consistent Laplacian (1 / m^2 times the
+        field's unit) of a prognostic field, a mixing ratio, ``vorticity``,
+        ``divergence``, ``pv``, ``u`` or ``v`` (the names ``latlon_field``
+        takes) on rank 0 (None elsewhere).  Shallow water, one process."""
+        from .models.geometry import lonlat_vectors
+        from .models.dissipation import primitives
+        from .ops.dissipation import laplacian_all
+        if self.physics.name != "swe":
+            raise ValueError(f"the Laplacian is defined for the shallow-water model, not {self.physics.name!r}")
+        if self.mode == "spmd":
+            raise ValueError("laplacian: one process per rank (spmd) is not supported")
+        (kind, k), = self._resolve_names([name], "laplacian")
+
+        def make(kind, j, x):
+            e = self.engines[j]
+            if kind in ("der", "mix"):
+                return x[k][None]
+            if kind == "prog":
+                return e.tiles_view()[k][None]
+            v = primitives(e.tiles_view()[:4])[1:4]
+            d = torch.as_tensor(np.moveaxis(lonlat_vectors(e.geo.center)[k], -1, 0), device=v.device)
+            return ((v[0] * d[0] + v[1] * d[1]) + v[2] * d[2])[None]
+        xs = self._source_groups([(kind, k)], make)[kind]
+        s = getattr(self, "_dspec", None) or {"order": 1, "nu": 1.0e5, "depth": None}
+        ds = [e.dissipation(s["order"], s["nu"], s["depth"]) for e in self.engines]
+        return self._gather_tiles({e.rank: y[0].detach().cpu().numpy()
+                                   for e, y in zip(self.engines, laplacian_all(ds, xs))})
+
     # ---- lat-lon output (models/latlon.py, ops/latlon.py) ---------------------------
     def latlon_names(self) -> List[str]:
         """What ``latlon_field`` / ``zonal_mean`` accept for this model."""

@@ -86,6 +86,39 @@ def make_physics(pc) -> Any:
     raise ValueError(f"unknown physics model {pc.model!r}")
 
 
+def dissipation_spec(pc) -> Optional[Dict[str, Any]]:
+    """``physics.dissipation`` checked and completed: {order, nu, interval,
+    depth}, or None when it is off."""
+    d = pc.dissipation
+    if d is None:
+        return None
+    if not isinstance(d, dict):
+        raise ValueError(f"physics.dissipation: {{order, nu, interval, depth}} expected, not {d!r}")
+    unknown = set(d) - {"order", "nu", "interval", "depth"}
+    if unknown:
+        raise ValueError(f"physics.dissipation: unknown key(s) {sorted(unknown)}")
+    order, nu, interval, depth = d.get("order"), d.get("nu"), d.get("interval", 1), d.get("depth", True)
+    if isinstance(order, bool) or order not in (1, 2):
+        raise ValueError(f"physics.dissipation: order must be 1 or 2, not {order!r}")
+    if isinstance(nu, str):                  # YAML 1.1 reads 1.0e5 (no sign in the exponent) as a string
+        try:
+            nu = float(nu)
+        except ValueError:
+            pass
+    if isinstance(nu, bool) or not isinstance(nu, (int, float)) or not nu > 0:
+        raise ValueError(f"physics.dissipation: nu must be a positive number, not {nu!r}")
+    if isinstance(interval, bool) or not isinstance(interval, int) or interval < 1:
+        raise ValueError(f"physics.dissipation: interval must be a positive integer, not {interval!r}")
+    if not isinstance(depth, bool):
+        raise ValueError(f"physics.dissipation: depth must be true or false, not {depth!r}")
+    if pc.model.lower() != "swe":
+        raise ValueError(f"physics.dissipation: defined for the shallow-water model, not {pc.model!r}")
+    if pc.tracers and depth:
+        raise ValueError("physics.dissipation with physics.tracers: only depth: false is accepted (diffusing h "
+                         "would change the mixing ratios hq / h)")
+    return {"order": int(order), "nu": float(nu), "interval": int(interval), "depth": depth}
+
+
 class _HostQueue:
     """Host work of the run loop, in submission order: ``append((event,
     work))`` runs ``work()`` once ``event`` (a CUDA event, or None) has
@@ -188,6 +221,8 @@ class Solver(SolverDiagnostics):
         self.comm = "local"
         self.mode = None
         self.world, self.rank = 1, 0
+        self._dspec = None            # physics.dissipation, checked (initialize)
+        self._dinterval = 0           # model steps between its applications (doubles when dt is halved)
 
     # ---- setup ------------------------------------------------------------
     def setup_sharding(self) -> None:
@@ -208,6 +243,10 @@ class Solver(SolverDiagnostics):
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
         self.rank = int(os.environ.get("RANK", "0"))
         local = int(os.environ.get("LOCAL_RANK", "0"))
+        self._dspec = dissipation_spec(c.physics)
+        if self._dspec is not None and self.world > 1:
+            raise ValueError("physics.dissipation: one process per rank (spmd) is not supported; run one "
+                             "rank or virtual ranks in one process")
         gpu = c.parallelization.device_type == "gpu"
         if gpu and not torch.cuda.is_available():
             raise RuntimeError("device_type 'gpu' requested but no GPU is visible (use device_type: cpu)")
@@ -231,6 +270,11 @@ class Solver(SolverDiagnostics):
             self.mode = "single" if nd == 1 else "virtual"
             device = torch.device("cuda:0") if gpu else torch.device("cpu")
         self.device = device
+        if self._dspec is not None:
+            self._dinterval = self._dspec["interval"]
+            if c.io.checkpoint_interval > 0 and c.io.checkpoint_interval % self._dinterval:
+                raise ValueError(f"io.checkpoint_interval = {c.io.checkpoint_interval} is not a multiple of "
+                                 f"physics.dissipation.interval = {self._dinterval}")
         backend = c.runtime.backend
         if backend == "auto":
             backend = "hip" if device.type == "cuda" else "torch"
@@ -568,15 +612,40 @@ class Solver(SolverDiagnostics):
         pieces of their interval with a particle advance after each."""
         if nsteps <= 0:
             return
-        if not self._particles:
+        div = self._dinterval if self._dspec is not None else 0
+        piv = self._pinterval if self._particles else 0
+        if not div and not piv:
             return self._step_model(nsteps)
-        iv = self._pinterval
-        if nsteps % iv:
+        if piv and nsteps % piv:
             raise ValueError(f"step({nsteps}): with particles attached the step count must be a multiple of "
-                             f"their interval {iv}")
-        for _ in range(nsteps // iv):
-            self._step_model(iv)
-            self._particles_advance()
+                             f"their interval {piv}")
+        if div and nsteps % div:
+            raise ValueError(f"step({nsteps}): with physics.dissipation the step count must be a multiple of "
+                             f"its interval {div}")
+        pos = 0
+        while pos < nsteps:      # pieces that end at the next dissipation or particle time
+            nxt = min((pos // v + 1) * v for v in (div, piv) if v)
+            self._step_model(nxt - pos)
+            pos = nxt
+            if div and pos % div == 0:
+                self.dissipate()
+            if piv and pos % piv == 0:
+                self._particles_advance()
+
+    def _dissipations(self):
+        """The dissipation operator of every engine of this process, as configured."""
+        if self._dspec is None:
+            raise ValueError("no dissipation configured (physics.dissipation)")
+        s = self._dspec
+        return [e.dissipation(s["order"], s["nu"], s["depth"]) for e in self.engines]
+
+    def dissipate(self, tau: Optional[float] = None) -> int:
+        """Apply the configured dissipation once over ``tau`` seconds (default:
+        its interval times dt), split into equal Euler sub-steps where the
+        explicit bound asks for it; returns their number."""
+        from .ops.dissipation import apply_all
+        ds = self._dissipations()
+        return apply_all(ds, self._dinterval * self.dt if tau is None else float(tau))
 
     def _step_model(self, nsteps: int) -> None:
         if self.mode == "virtual":
@@ -640,6 +709,10 @@ class Solver(SolverDiagnostics):
         particles = self._particles
         if particles:                            # chunks end at particle times
             iv["particles"] = self._pinterval
+        dissipation = self._dspec is not None
+        if dissipation:                          # ... and at dissipation times
+            iv["dissipation"] = self._dspec["interval"]
+            self._dinterval = self._dspec["interval"]
         iv = {k: v * SUB for k, v in iv.items() if v > 0}
         hist = None
         if "history" in iv:
@@ -717,6 +790,8 @@ class Solver(SolverDiagnostics):
                 self.runner.graph_periods = max(1, min(max(lens), 512) // per)
                 for k in lens[:8]:
                     self.runner.prepare(k)      # chunks shorter than a period: their remainder launch
+            if dissipation:
+                self._dissipations()             # tables and buffers, before the clock starts
             if deferred and ("watchdog" in iv or "metrics" in iv):
                 self._warm_checks(derived="metrics" in iv)
             self._sync()
@@ -735,6 +810,9 @@ class Solver(SolverDiagnostics):
             done += chunk
             drain()
             p = pos()
+            if dissipation and p % iv["dissipation"] == 0:
+                with ph("dissipation"):
+                    self.dissipate()
             if particles and p % iv["particles"] == 0:
                 with ph("particles"):
                     self._particles_advance()
@@ -770,6 +848,8 @@ class Solver(SolverDiagnostics):
                     self.set_dt(dt_cur * 0.5)
                     if abs(self.dt * (1 << level) - dt0) > 1e-9 * dt0:
                         self.set_dt(dt0 / (1 << level))
+                    if dissipation:              # tau stays put: twice the steps between applications
+                        self._dinterval = self._dspec["interval"] << level
                     if particles:                # the particle times stay put: twice the steps between them
                         for P in particles:
                             P.interval = self._pinterval << level

@@ -255,6 +255,20 @@ class Engine:
         from .ops.points import Particles
         return Particles(self, lonlat_points(lat, lon), interval)
 
+    def dissipation(self, order: int = 1, nu: float = 1.0e5, depth: Optional[bool] = None):
+        """``ops.dissipation.Dissipation`` of this engine (shallow water): the
+        consistent Laplacian applied once (``order`` 1, ``nu`` in m^2/s) or twice
+        (2, m^4/s), with (``depth``; default: unless tracers ride along) or
+        without the free surface; built on first use and cached per setting."""
+        from .ops.dissipation import Dissipation
+        if depth is None:
+            depth = not getattr(self.physics, "nq", 0)
+        key = (order, float(nu), bool(depth))
+        cache = self.__dict__.setdefault("_dissipation", {})
+        if key not in cache:
+            cache[key] = Dissipation(self, *key)
+        return cache[key]
+
     def spectra(self, lmax: int):
         """``ops.spectra.Spectra`` of this engine up to degree ``lmax``, built
         on first use and cached per ``lmax``."""

@@ -11,6 +11,9 @@ invariant representation the reference exchanges across cube edges (PDF s.18
 * ``williamson_tc2``    steady geostrophic flow (analytic solution = IC).
 * ``williamson_tc5``    zonal flow over an isolated mountain.
 * ``williamson_tc6``    Rossby-Haurwitz wave, wavenumber 4.
+* ``galewsky``          barotropically unstable jet (Galewsky, Scott & Polvani
+                        2004), balanced depth by quadrature, with or without
+                        the perturbation.
 * ``tracer_field``      mixing ratios in [0, 1] for the shallow-water tracers:
                         ``constant``, ``cosine_bell``, ``cap``, ``gradient``.
 * ``lima_flag``         checkerboard heat source on the top panel (face 0) on a
@@ -114,6 +117,78 @@ def williamson_tc6(p, radius=EARTH_RADIUS, omega=OMEGA, g=GRAVITY, w=7.848e-6, K
     e, n = lonlat_vectors(p)
     wind = u[..., None] * e + v[..., None] * n
     return gh / g, wind, np.zeros_like(gh)
+
+
+# ---- Galewsky, Scott & Polvani (2004): the barotropically unstable jet ---------------------
+GALEWSKY_PHI0 = math.pi / 7.0
+GALEWSKY_PHI1 = 0.5 * math.pi - GALEWSKY_PHI0
+GALEWSKY_UMAX = 80.0
+GALEWSKY_MEAN_DEPTH = 10000.0
+GALEWSKY_PANELS = 64          # quadrature panels across the jet
+GALEWSKY_NODES = 16           # Gauss-Legendre nodes per panel
+
+
+def galewsky_wind(lat):
+    """u(phi) = (80 / e_n) exp[1 / ((phi - phi0)(phi - phi1))] inside the jet
+    phi0 < phi < phi1, 0 elsewhere; e_n = exp[-4 / (phi1 - phi0)^2]."""
+    lat = np.asarray(lat, dtype=np.float64)
+    p0, p1 = GALEWSKY_PHI0, GALEWSKY_PHI1
+    inside = (lat > p0) & (lat < p1)
+    x = np.where(inside, (lat - p0) * (lat - p1), -1.0)
+    en = math.exp(-4.0 / (p1 - p0) ** 2)
+    return np.where(inside, GALEWSKY_UMAX / en * np.exp(1.0 / x), 0.0)
+
+
+def _galewsky_integrand(lat, radius, omega):
+    u = galewsky_wind(lat)
+    return radius * u * (2.0 * omega * np.sin(lat) + u * np.tan(lat) / radius)
+
+
+def _gauss_on(a, b, fn, nodes):
+    """Gauss-Legendre quadrature of fn over [a, b] (arrays of equal shape)."""
+    x, w = np.polynomial.legendre.leggauss(nodes)
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    half, mid = 0.5 * (b - a), 0.5 * (b + a)
+    return half * (fn(mid[..., None] + half[..., None] * x) * w).sum(-1)
+
+
+def galewsky_depth(lat, radius=EARTH_RADIUS, omega=OMEGA, g=GRAVITY, nodes=GALEWSKY_NODES):
+    """Balanced depth h(phi) of the jet (m):
+    g h(phi) = g h0 - int_{-pi/2}^{phi} a u (f + u tan(phi') / a) dphi'
+    by composite Gauss-Legendre quadrature on the host (``GALEWSKY_PANELS``
+    fixed panels across the jet with ``nodes`` nodes each, and a last partial
+    panel up to phi); h0 makes the analytic global mean depth 10 000 m."""
+    lat = np.asarray(lat, dtype=np.float64)
+    p0, p1, K = GALEWSKY_PHI0, GALEWSKY_PHI1, GALEWSKY_PANELS
+    fn = lambda x: _galewsky_integrand(x, radius, omega)
+    edges = np.linspace(p0, p1, K + 1)
+    cum = np.concatenate([[0.0], np.cumsum(_gauss_on(edges[:-1], edges[1:], fn, nodes))])
+    x = np.clip(lat, p0, p1)
+    k = np.minimum(((x - p0) / (p1 - p0) * K).astype(np.int64), K - 1)
+    I = cum[k] + _gauss_on(edges[k], x, fn, nodes)
+    # mean of I over the sphere = 1/2 int I cos = 1/2 (I(phi1) - int_jet I' sin) by parts
+    mean_I = 0.5 * (cum[-1] - _gauss_on(edges[:-1], edges[1:], lambda y: fn(y) * np.sin(y), nodes).sum())
+    return GALEWSKY_MEAN_DEPTH + (mean_I - I) / g
+
+
+def galewsky_perturbation(lon, lat):
+    """120 cos(phi) exp[-(lambda / (1/3))^2] exp[-((pi/4 - phi) / (1/15))^2] m,
+    lambda in (-pi, pi]."""
+    lam = np.mod(np.asarray(lon, dtype=np.float64) + math.pi, 2.0 * math.pi) - math.pi
+    lat = np.asarray(lat, dtype=np.float64)
+    return 120.0 * np.cos(lat) * np.exp(-(lam * 3.0) ** 2) * np.exp(-((0.25 * math.pi - lat) * 15.0) ** 2)
+
+
+def galewsky(p, perturbed=True, radius=EARTH_RADIUS, omega=OMEGA, g=GRAVITY):
+    """The barotropically unstable jet of Galewsky, Scott & Polvani (2004):
+    the balanced zonal jet, with the depth perturbation that triggers the
+    instability (``perturbed``).  Returns (h, wind, b = 0)."""
+    lon, lat = xyz_to_lonlat(p)
+    h = galewsky_depth(lat, radius, omega, g)
+    if perturbed:
+        h = h + galewsky_perturbation(lon, lat)
+    e, _ = lonlat_vectors(p)
+    return h, galewsky_wind(lat)[..., None] * e, np.zeros_like(h)
 
 
 def lima_flag(N: int, squares: int = 8, hot: float = 1000.0, background: float = 1.0) -> np.ndarray:

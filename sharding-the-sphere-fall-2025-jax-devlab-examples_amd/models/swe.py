@@ -56,6 +56,9 @@ class ShallowWater(Physics):
             h, wind, b = ic.williamson_tc5(p, radius=grid.radius, omega=self.omega, g=self.g)
         elif self.case == "tc6":
             h, wind, b = ic.williamson_tc6(p, radius=grid.radius, omega=self.omega, g=self.g)
+        elif self.case in ("galewsky", "galewsky_balanced"):
+            h, wind, b = ic.galewsky(p, perturbed=self.case == "galewsky", radius=grid.radius, omega=self.omega,
+                                     g=self.g)
         elif self.case == "rest":
             h = np.full(p.shape[:-1], 1000.0)
             wind = np.zeros(p.shape)

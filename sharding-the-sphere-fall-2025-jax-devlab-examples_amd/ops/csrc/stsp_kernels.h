@@ -319,6 +319,42 @@ typedef struct PointsDesc {
 } PointsDesc;
 int stsp_points_launch(int dtype, const PointsDesc* d, hipStream_t stream);
 int stsp_points_desc_size(void);
+// Scale-selective dissipation of the shallow-water state (dissipation_kernel.hip,
+// ops/dissipation.py; the scheme, the tables and the twin in models/dissipation.py):
+// one ordinary launch per pass, one workgroup per 16 x 16 cell block.  Pass 1
+// writes the four scalars and their least-squares gradients to the scratch, pass
+// 2 forms the corrected edge fluxes from the scratch alone and either stores L w
+// or updates the state in place.  All arithmetic and every table is float64;
+// `dtype` is the element type of the state.
+typedef struct DissDesc {
+  const void* src;      // pass 1 in: mode 1 the state [F][S] (element type), mode 0 scalars [4][S] (double)
+  const void* recv;     // pass 1 in: remote ghosts of src, [R][recv_stride], type of src (nullable when R == 0)
+  double* scratch;      // [16][S]: rows 0..3 scalars, row 4 + 3 c + k component k of G of scalar c
+  const double* srecv;  // pass 2 in: remote ghosts of scratch [R][16] (nullable when R == 0)
+  void* out;            // pass 2 out: mode 0 L w [4][S] (double), mode 1 the state [F][S] (element type)
+  const int* gmap;      // [T][4][mg][n] ghost map (layer 0 is read)
+  const double* W;      // [4][3][T][n][n] gradient weights of the neighbours W, E, S, N
+  const double* cx;     // [T][n][n+1] L / dn of the x-edges
+  const double* cy;     // [T][n+1][n]
+  const double* kx;     // [3][T][n][n+1] L (m - dvec / dn)
+  const double* ky;     // [3][T][n+1][n]
+  const double* gb;     // [3][T][n][n] G(b)
+  const double* dbx;    // [T][n][n+1] b_R - b_L
+  const double* dby;    // [T][n+1][n]
+  const double* invA;   // [T][n][n]
+  const double* ctr;    // [3][T][n][n] unit cell centres
+  int ntile, n, S, mg, pw;  // as StageDesc
+  int nrecv;            // rows of recv / srecv
+  int recv_stride;      // pass 1: values per row of recv (>= 4)
+  int nblocks;          // ntile * ceil(n / 16)^2
+  int pass_;            // 1 gradients, 2 fluxes
+  int mode;             // pass 1: 1 = src is (h, M), read as (h, M / h); pass 2: 1 = update the state
+  int use_b;            // add the topography terms to scalar 0
+  int depth;            // update: write h
+  double coef;          // update: w += coef L w
+} DissDesc;
+int stsp_dissipation_launch(int dtype, const DissDesc* d, hipStream_t stream);
+int stsp_dissipation_desc_size(void);
 // Direct xGMI halo build constant: ring slots.
 int stsp_xg_slots(void);
 }

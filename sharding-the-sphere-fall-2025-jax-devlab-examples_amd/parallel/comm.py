@@ -145,6 +145,14 @@ class VirtualHub:
     def __init__(self):
         self.sends: Dict[int, torch.Tensor] = {}
         self.plans: Dict[int, RankPlan] = {}
+        self._subs: Dict = {}
+
+    def sub(self, key) -> "VirtualHub":
+        """A mailbox of its own for another traffic of the same ranks (buffers
+        of another row count), shared by everyone who asks with ``key``."""
+        if key not in self._subs:
+            self._subs[key] = VirtualHub()
+        return self._subs[key]
 
     def transport(self, plan, F, dtype, device) -> "VirtualTransport":
         self.plans[plan.rank] = plan

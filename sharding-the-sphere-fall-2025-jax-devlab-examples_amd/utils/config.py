@@ -48,7 +48,7 @@ class GridConfig:
 @dataclass
 class PhysicsConfig:
     model: str = "swe"            # swe | advection | diffusion | planar_swe (single flat panel)
-    case: Optional[str] = None    # tc2 | tc5 | tc6 | rest | cosine_bell | gaussian | lima_flag
+    case: Optional[str] = None    # tc2 | tc5 | tc6 | galewsky | galewsky_balanced | rest | cosine_bell | gaussian | lima_flag
     limiter: str = "mc"
     alpha: float = 0.0
     kappa: float = 2.0e6
@@ -56,6 +56,11 @@ class PhysicsConfig:
     # the flow (models/initial_conditions.py::tracer_field: constant | cosine_bell |
     # cap | gradient); null or empty = none
     tracers: Optional[List[str]] = None
+    # shallow water only: scale-selective dissipation applied between model steps
+    # (models/dissipation.py): {order: 1 | 2, nu: m^2/s (order 1) or m^4/s (order 2),
+    # interval: steps between applications (default 1), depth: diffuse the free
+    # surface too (default true; false with tracers)}; null = off
+    dissipation: Optional[Dict[str, Any]] = None
 
 
 @dataclass
