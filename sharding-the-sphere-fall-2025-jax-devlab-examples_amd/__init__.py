@@ -17,7 +17,7 @@ from .models.geometry import CubedSphereGrid
 from .models.integrators import get_integrator
 from .models.swe import ShallowWater
 from .models.advection import Advection
-from .models.diffusion import Diffusion
+from .models.diffusion import ConsistentDiffusion, Diffusion
 from .ops.halo import (exchange_edge_pair, extract_boundary_data, make_halo_exchange, set_ghost_data,
                        remove_ghosts, add_ghosts)
 from .engine import Engine, GraphStepper, VirtualCluster
@@ -28,7 +28,8 @@ __all__ = [
     "apply_operations", "create_communication_schedule", "derive_edge_pairs", "edge_coloring", "neighbor_cell",
     "num_tiles", "partition_tiles", "valid_device_counts", "validate_device_count", "TileLayout", "RankPlan",
     "TileMesh", "TileSharding", "setup_sharding", "Config", "load_config", "save_config", "CubedSphereGrid",
-    "get_integrator", "ShallowWater", "Advection", "Diffusion", "exchange_edge_pair", "extract_boundary_data",
+    "get_integrator", "ShallowWater", "Advection", "Diffusion", "ConsistentDiffusion", "exchange_edge_pair",
+    "extract_boundary_data",
     "make_halo_exchange", "set_ghost_data", "remove_ghosts", "add_ghosts", "Engine", "GraphStepper",
     "VirtualCluster", "Solver", "make_physics", "Ensemble",
 ]

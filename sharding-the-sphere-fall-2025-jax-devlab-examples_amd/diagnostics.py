@@ -193,14 +193,19 @@ class SolverDiagnostics:
         """[6, N, N] float64 of the consistent Laplacian (1 / m^2 times the
         field's unit) of a prognostic field, a mixing ratio, ``vorticity``,
         ``divergence``, ``pv``, ``u`` or ``v`` (the names ``latlon_field``
-        takes) on rank 0 (None elsewhere).  Shallow water, one process."""
+        takes) on rank 0 (None elsewhere); of the advection and diffusion models,
+        their prognostic field (ops/heat.py).  One process."""
         from .models.geometry import lonlat_vectors
         from .models.dissipation import primitives
         from .ops.dissipation import laplacian_all
-        if self.physics.name != "swe":
-            raise ValueError(f"the Laplacian is defined for the shallow-water model, not {self.physics.name!r}")
         if self.mode == "spmd":
             raise ValueError("laplacian: one process per rank (spmd) is not supported")
+        if self.physics.name != "swe":
+            from .ops import heat
+            if name not in self.fields:
+                raise ValueError(f"unknown laplacian field {name!r}; choose from {list(self.fields)}")
+            Ls = heat.laplacian_all([e.heat_operator() for e in self.engines])
+            return self._gather_tiles({e.rank: y.detach().cpu().numpy() for e, y in zip(self.engines, Ls)})
         (kind, k), = self._resolve_names([name], "laplacian")
 
         def make(kind, j, x):

@@ -35,7 +35,7 @@ from .engine import Engine, VirtualCluster
 from .models.advection import Advection
 from .models.base import limiter_code
 from .models.derived import FIELDS as DERIVED_FIELDS, INVARIANTS
-from .models.diffusion import Diffusion
+from .models.diffusion import OPERATORS, ConsistentDiffusion, Diffusion
 from .models.geometry import DAY, EARTH_RADIUS, CubedSphereGrid
 from .models.spectra import check_lmax
 from .models.swe import MAX_TRACERS, ShallowWater, ShallowWaterTracers
@@ -75,6 +75,11 @@ def make_physics(pc) -> Any:
                          f"not {tracers!r}")
     if tracers and model != "swe":
         raise ValueError(f"physics.tracers: tracers are carried by the shallow-water model, not {model!r}")
+    op = pc.operator
+    if op not in OPERATORS:
+        raise ValueError(f"physics.operator: one of {list(OPERATORS)} expected, not {op!r}")
+    if op == "consistent" and model != "diffusion":
+        raise ValueError(f"physics.operator: consistent is defined for the diffusion model, not {model!r}")
     if model == "swe":
         if tracers:
             return ShallowWaterTracers(case, tracers=list(tracers), limiter=lim, alpha=pc.alpha)
@@ -82,7 +87,11 @@ def make_physics(pc) -> Any:
     if model == "advection":
         return Advection(case, alpha=pc.alpha, limiter=lim)
     if model == "diffusion":
-        return Diffusion(kappa=pc.kappa, case=case)
+        try:                                     # YAML 1.1 reads 2.0e6 (no sign in the exponent) as a string
+            kappa = float(pc.kappa)
+        except (TypeError, ValueError):
+            raise ValueError(f"physics.kappa: a number expected, not {pc.kappa!r}") from None
+        return (ConsistentDiffusion if op == "consistent" else Diffusion)(kappa=kappa, case=case)
     raise ValueError(f"unknown physics model {pc.model!r}")
 
 
@@ -246,6 +255,9 @@ class Solver(SolverDiagnostics):
         self._dspec = dissipation_spec(c.physics)
         if self._dspec is not None and self.world > 1:
             raise ValueError("physics.dissipation: one process per rank (spmd) is not supported; run one "
+                             "rank or virtual ranks in one process")
+        if c.physics.operator == "consistent" and self.world > 1:
+            raise ValueError("physics.operator: consistent: one process per rank (spmd) is not supported; run one "
                              "rank or virtual ranks in one process")
         gpu = c.parallelization.device_type == "gpu"
         if gpu and not torch.cuda.is_available():
@@ -469,6 +481,8 @@ class Solver(SolverDiagnostics):
         c = self.cfg.runtime
         if self.backend != "hip" or c.canary:
             return False
+        if getattr(self.physics, "two_pass", False):
+            return False                 # two launches and an exchange per stage: eager, through Engine.step
         if self.mode == "single":
             return c.graph
         return self.mode == "spmd" and self.comm in ("xgmi", "rccl", "ipc")

@@ -11,6 +11,11 @@ A time step is the integrator's stage list; each stage is
 With ``backend='torch'`` compute is the PyTorch reference (CPU or GPU); with
 ``backend='hip'`` it is the fused gfx950 stage kernel (``ops/csrc``), and the
 ``NativeRuntime`` can take over the whole step loop (C++ + hipGraph + RCCL).
+
+A physics with ``two_pass`` (the consistent diffusion) steps through
+``ops.heat.ConsistentCompute`` on either backend: its stages have a middle phase
+(``stage_mid``: finish the exchange of Q, first pass, start the exchange of its
+scratch) between ``stage_begin`` and ``stage_end``, and an ``end_step`` hook.
 """
 from __future__ import annotations
 
@@ -93,13 +98,18 @@ class Engine:
         self._latlon: Dict[tuple, object] = {}      # ops.latlon.LatLon per target grid (latlon())
         self._spectra: Dict[int, object] = {}       # ops.spectra.Spectra per lmax (spectra())
         self.block = tuple(block) if block is not None else None   # None: ops.hip_compute.choose_block
-        if backend == "torch":
+        if backend not in ("torch", "hip"):
+            raise ValueError(f"unknown backend {backend!r}")
+        if getattr(physics, "two_pass", False):
+            # two passes per stage with an exchange between them (ops/heat.py): the
+            # gfx950 kernels with backend 'hip' on a GPU, else the PyTorch twin
+            from .ops.heat import ConsistentCompute
+            self.compute = ConsistentCompute(self)
+        elif backend == "torch":
             self.compute = TorchCompute(self)
-        elif backend == "hip":
+        else:
             from .ops.hip_compute import HipCompute
             self.compute = HipCompute(self)
-        else:
-            raise ValueError(f"unknown backend {backend!r}")
 
     # ---- state ------------------------------------------------------------
     @property
@@ -159,8 +169,12 @@ class Engine:
     # ---- stepping -----------------------------------------------------------
     canary = False   # debug race screen, HIP backend, eager only
 
+    def _canary(self) -> bool:
+        # the screen checks the stage kernel's ghost pushes; the two-pass path pushes none
+        return self.canary and self.backend == "hip" and getattr(self.compute, "stage_mid", None) is None
+
     def stage_begin(self, st: Stage) -> None:
-        if self.canary and self.backend == "hip":
+        if self._canary():
             # every same-rank ghost slot of the output must be re-pushed this stage
             self.pool[st.out][:, self.halo_dst] = float("nan")
             if self.transport.recv.numel():
@@ -168,13 +182,21 @@ class Engine:
         self.transport.start(self.pool[st.Q])
         self.compute.stage(st, self.dt, None, part="interior")
 
+    def stage_mid(self, st: Stage) -> None:
+        """The optional phase between ``stage_begin`` and ``stage_end`` of a
+        compute class with two passes per stage (``stage_mid``): it consumes the
+        exchange of Q and may start one of its own.  Nothing for the others."""
+        mid = getattr(self.compute, "stage_mid", None)
+        if mid is not None:
+            mid(st, self.dt, self.transport.finish())
+
     def stage_end(self, st: Stage) -> None:
-        recv = self.transport.finish()
-        if self.canary and self.backend == "hip" and recv is not None and recv.numel():
+        recv = self.transport.finish() if getattr(self.compute, "stage_mid", None) is None else None
+        if self._canary() and recv is not None and recv.numel():
             if not bool(torch.isfinite(recv).all()):
                 raise RuntimeError("canary: a remote ghost slot was not delivered by the exchange")
         self.compute.stage(st, self.dt, recv, part="boundary")
-        if self.canary and self.backend == "hip":
+        if self._canary():
             out = self.pool[st.out]
             bad = ~torch.isfinite(out[:, self.halo_dst])
             if bool(bad.any()):
@@ -185,11 +207,15 @@ class Engine:
         self.pool = [self.pool[r] for r in rot]
         self.time += self.dt
         self.step_count += 1
+        fin = getattr(self.compute, "end_step", None)
+        if fin is not None:
+            fin()
 
     def step(self, nsteps: int = 1) -> None:
         for _ in range(nsteps):
             for st in self.integ.stages:
                 self.stage_begin(st)
+                self.stage_mid(st)
                 self.stage_end(st)
             self.end_step()
 
@@ -268,6 +294,16 @@ class Engine:
         if key not in cache:
             cache[key] = Dissipation(self, *key)
         return cache[key]
+
+    def heat_operator(self):
+        """``ops.heat.HeatOperator`` of this engine (the consistent Laplacian of
+        its scalar field): the two-pass compute class's own, else built on first use."""
+        from .ops.heat import ConsistentCompute, HeatOperator
+        if isinstance(self.compute, ConsistentCompute):
+            return self.compute.op
+        if getattr(self, "_heat", None) is None:
+            self._heat = HeatOperator(self)
+        return self._heat
 
     def spectra(self, lmax: int):
         """``ops.spectra.Spectra`` of this engine up to degree ``lmax``, built
@@ -372,6 +408,8 @@ class VirtualCluster:
             for st in self.engines[0].integ.stages:
                 for e in self.engines:
                     e.stage_begin(st)
+                for e in self.engines:
+                    e.stage_mid(st)
                 for e in self.engines:
                     e.stage_end(st)
             for e in self.engines:

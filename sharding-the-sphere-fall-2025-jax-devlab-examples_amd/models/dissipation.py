@@ -161,6 +161,34 @@ def primitives(q: torch.Tensor) -> torch.Tensor:
     return torch.stack([h, q[1] / safe, q[2] / safe, q[3] / safe])
 
 
+def ls_gradient(W: torch.Tensor, w: torch.Tensor, n: int):
+    """The shared arithmetic of pass 1: of the one-ring window w [C, T, n+2, n+2]
+    (corners unused) the interior values c [C, T, n, n] and the three Cartesian
+    components of G = sum_k W_k (w_k - w_i), each [C, T, n, n]."""
+    c = w[:, :, 1:n + 1, 1:n + 1]
+    d = (w[:, :, 1:n + 1, 0:n] - c, w[:, :, 1:n + 1, 2:n + 2] - c, w[:, :, 0:n, 1:n + 1] - c,
+         w[:, :, 2:n + 2, 1:n + 1] - c)
+    return c, [((W[0, k] * d[0] + W[1, k] * d[1]) + W[2, k] * d[2]) + W[3, k] * d[3] for k in range(3)]
+
+
+def corrected_divergence(s: torch.Tensor, G: torch.Tensor, tabs: Dict[str, torch.Tensor], n: int,
+                         db=None) -> torch.Tensor:
+    """The shared arithmetic of pass 2: L s [C, T, n, n] of the one-ring windows
+    s [C, T, n+2, n+2] and G [C, 3, T, n+2, n+2] (corners unused); ``db`` =
+    (dbx, dby): the topography differences added to scalar 0."""
+    kx, ky = tabs["kx"], tabs["ky"]
+    dx = s[:, :, 1:n + 1, 1:n + 2] - s[:, :, 1:n + 1, 0:n + 1]                    # [C,T,n,n+1]
+    dy = s[:, :, 1:n + 2, 1:n + 1] - s[:, :, 0:n + 1, 1:n + 1]
+    if db is not None:
+        dx = torch.cat([(dx[0] + db[0])[None], dx[1:]])
+        dy = torch.cat([(dy[0] + db[1])[None], dy[1:]])
+    gx = G[:, :, :, 1:n + 1, 0:n + 1] + G[:, :, :, 1:n + 1, 1:n + 2]            # [C,3,T,n,n+1]
+    gy = G[:, :, :, 0:n + 1, 1:n + 1] + G[:, :, :, 1:n + 2, 1:n + 1]
+    px = tabs["cx"] * dx + 0.5 * ((gx[:, 0] * kx[0] + gx[:, 1] * kx[1]) + gx[:, 2] * kx[2])
+    py = tabs["cy"] * dy + 0.5 * ((gy[:, 0] * ky[0] + gy[:, 1] * ky[1]) + gy[:, 2] * ky[2])
+    return ((px[..., 1:] - px[..., :-1]) + (py[..., 1:, :] - py[..., :-1, :])) * tabs["invA"]
+
+
 def gradient_pass(src: torch.Tensor, recv: Optional[torch.Tensor], gmap: torch.Tensor, tabs: Dict[str, torch.Tensor],
                   T: int, n: int, ng: int, swe: bool, use_b: bool, scratch: torch.Tensor) -> None:
     """Pass 1: the four scalars of the padded buffer ``src`` [>= 4, S] (``swe``:
@@ -169,15 +197,12 @@ def gradient_pass(src: torch.Tensor, recv: Optional[torch.Tensor], gmap: torch.T
     w = extend(src[:4], None if recv is None else recv[:, :4], gmap, T, n, 1, ng=ng).to(torch.float64)
     if swe:
         w = primitives(w)
-    c = w[:, :, 1:n + 1, 1:n + 1]
-    d = (w[:, :, 1:n + 1, 0:n] - c, w[:, :, 1:n + 1, 2:n + 2] - c, w[:, :, 0:n, 1:n + 1] - c,
-         w[:, :, 2:n + 2, 1:n + 1] - c)
-    W = tabs["W"]
+    c, G = ls_gradient(tabs["W"], w, n)
     P = n + 2 * ng
     sv = scratch.view(ROWS, T, P, P)[:, :, ng:ng + n, ng:ng + n]
     sv[0:4] = c
     for k in range(3):
-        g = ((W[0, k] * d[0] + W[1, k] * d[1]) + W[2, k] * d[2]) + W[3, k] * d[3]      # [4,T,n,n]
+        g = G[k]                                                                       # [4,T,n,n]
         if use_b:
             g = torch.cat([(g[0] + tabs["gb"][k])[None], g[1:]])
         for s in range(4):
@@ -188,19 +213,8 @@ def flux_pass(scratch: torch.Tensor, srecv: Optional[torch.Tensor], gmap: torch.
               tabs: Dict[str, torch.Tensor], T: int, n: int, ng: int, use_b: bool) -> torch.Tensor:
     """Pass 2: L of the four scalars [4, T, n, n] from the scratch buffer."""
     w = extend(scratch, srecv, gmap, T, n, 1, ng=ng)                            # [16,T,n+2,n+2]
-    s = w[0:4]
-    G = w[4:].reshape(4, 3, T, n + 2, n + 2)
-    kx, ky = tabs["kx"], tabs["ky"]
-    dx = s[:, :, 1:n + 1, 1:n + 2] - s[:, :, 1:n + 1, 0:n + 1]                    # [4,T,n,n+1]
-    dy = s[:, :, 1:n + 2, 1:n + 1] - s[:, :, 0:n + 1, 1:n + 1]
-    if use_b:
-        dx = torch.cat([(dx[0] + tabs["dbx"])[None], dx[1:]])
-        dy = torch.cat([(dy[0] + tabs["dby"])[None], dy[1:]])
-    gx = G[:, :, :, 1:n + 1, 0:n + 1] + G[:, :, :, 1:n + 1, 1:n + 2]            # [4,3,T,n,n+1]
-    gy = G[:, :, :, 0:n + 1, 1:n + 1] + G[:, :, :, 1:n + 2, 1:n + 1]
-    px = tabs["cx"] * dx + 0.5 * ((gx[:, 0] * kx[0] + gx[:, 1] * kx[1]) + gx[:, 2] * kx[2])
-    py = tabs["cy"] * dy + 0.5 * ((gy[:, 0] * ky[0] + gy[:, 1] * ky[1]) + gy[:, 2] * ky[2])
-    return ((px[..., 1:] - px[..., :-1]) + (py[..., 1:, :] - py[..., :-1, :])) * tabs["invA"]
+    return corrected_divergence(w[0:4], w[4:].reshape(4, 3, T, n + 2, n + 2), tabs, n,
+                                (tabs["dbx"], tabs["dby"]) if use_b else None)
 
 
 def update(q: torch.Tensor, Lw: torch.Tensor, coef: float, tabs: Dict[str, torch.Tensor], depth: bool) -> None:

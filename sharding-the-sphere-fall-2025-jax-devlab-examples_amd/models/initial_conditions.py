@@ -207,6 +207,21 @@ def gaussian_hill(p, center=(1.0, 0.0, 0.0), width=0.3, amp=1.0):
     return amp * np.exp(-d2 / (width * width))
 
 
+# ---- spherical harmonics with a closed-form heat solution (models/diffusion.py) -----
+# name: (degree l, Y(p) at unit positions p[..., 3], an unnormalised harmonic of that degree)
+HARMONICS = {
+    "harmonic": (4, lambda p: 35.0 * p[..., 2] ** 4 - 30.0 * p[..., 2] ** 2 + 3.0),                   # zonal
+    "harmonic32": (3, lambda p: p[..., 2] * (p[..., 0] ** 2 - p[..., 1] ** 2)),                       # l = 3, m = 2
+}
+
+
+def harmonic_decay(name, p, t, kappa, radius=EARTH_RADIUS):
+    """The solution of dT/dt = kappa lap T from the harmonic ``name`` at time t:
+    Y(p) exp(-l (l + 1) kappa t / R^2)."""
+    l, Y = HARMONICS[name]
+    return Y(np.asarray(p, dtype=np.float64)) * math.exp(-l * (l + 1) * kappa * t / (radius * radius))
+
+
 # ---- shallow-water tracers (models/swe.py::ShallowWaterTracers) ------------------
 # centre (lon, lat) and angular radius of the ``cap`` tracer
 CAP_CENTER = (0.6, 0.3)

@@ -355,6 +355,43 @@ typedef struct DissDesc {
 } DissDesc;
 int stsp_dissipation_launch(int dtype, const DissDesc* d, hipStream_t stream);
 int stsp_dissipation_desc_size(void);
+// Consistent thermal diffusion (heat_kernel.hip, ops/heat.py; the twin in
+// models/diffusion.py): the Laplacian of the dissipation for one scalar, fused
+// with the Runge-Kutta stage combination.  One ordinary launch per pass, one
+// workgroup per 16 x 16 cell block.  Pass 1 writes the scalar and its
+// least-squares gradient to the scratch; pass 2 forms L from the scratch alone
+// and stores L (mode 0), out = a2dt kappa L (+ a1 Q) (+ a0 X) (mode 1), or that
+// and acc_out = c1 X + c2dt kappa L (+ c0 ACC) (mode 2).  All arithmetic and every
+// table is float64; `dtype` is the element type of q, x, acc_in, out, acc_out.
+typedef struct HeatDesc {
+  const void* q;        // the stage input, one row [S] (element type); pass 2: read at the own cell only
+  const void* recv;     // pass 1: remote ghosts of q, [R][recv_stride], element 0 of a row (nullable when R == 0)
+  double* scratch;      // [4][S]: T, Gx, Gy, Gz
+  const double* srecv;  // pass 2: remote ghosts of scratch, [R][4] (nullable when R == 0)
+  const int* gmap;      // [T][4][mg][n]; layer 0 is read: >= 0 an interior cell of this rank, < 0 receive row -1 - code
+  const double* W;      // [4][3][T][n][n]
+  const double* cx;     // [T][n][n+1]
+  const double* cy;     // [T][n+1][n]
+  const double* kx;     // [3][T][n][n+1]
+  const double* ky;     // [3][T][n+1][n]
+  const double* invA;   // [T][n][n]
+  const void* x;        // modes 1, 2: X, one row [S] (read when a0 != 0 or mode 2; may alias out)
+  const void* acc_in;   // mode 2: ACC, one row [S] (nullable: no accumulator input; may alias acc_out)
+  void* out;            // modes 1, 2: one row [S]
+  void* acc_out;        // mode 2: one row [S]
+  double* lout;         // mode 0: L, one row [S] (double)
+  int ntile, n, S, mg, pw;   // S = ntile * pw * pw, pw = n + 2 mg
+  int nrecv;            // R
+  int recv_stride;      // elements per row of recv (pass 1)
+  int nblocks;          // ntile * ceil(n / 16)^2
+  int pass_;            // 1 or 2
+  int mode;             // pass 2: 0, 1 or 2
+  double kappa;
+  double a0, a1, a2dt;  // a2dt = a2 * dt
+  double c0, c1, c2dt;  // c2dt = c2 * dt
+} HeatDesc;
+int stsp_heat_launch(int dtype, const HeatDesc* d, hipStream_t stream);
+int stsp_heat_desc_size(void);
 // Direct xGMI halo build constant: ring slots.
 int stsp_xg_slots(void);
 }

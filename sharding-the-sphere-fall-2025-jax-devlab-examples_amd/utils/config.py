@@ -48,10 +48,15 @@ class GridConfig:
 @dataclass
 class PhysicsConfig:
     model: str = "swe"            # swe | advection | diffusion | planar_swe (single flat panel)
-    case: Optional[str] = None    # tc2 | tc5 | tc6 | galewsky | galewsky_balanced | rest | cosine_bell | gaussian | lima_flag
+    case: Optional[str] = None    # tc2 | tc5 | tc6 | galewsky | galewsky_balanced | rest | cosine_bell | gaussian | lima_flag | harmonic | harmonic32
     limiter: str = "mc"
     alpha: float = 0.0
     kappa: float = 2.0e6
+    # diffusion only: the Laplacian.  two_point: the flux kappa L / d across every edge
+    # (conservative, monotone, not consistent: the error does not fall under
+    # refinement); consistent: the corrected flux of models/dissipation.py (second
+    # order, conservative, not monotone; two launches per stage, eager stepping)
+    operator: str = "two_point"
     # shallow water only: initial conditions of up to 4 passive tracers carried by
     # the flow (models/initial_conditions.py::tracer_field: constant | cosine_bell |
     # cap | gradient); null or empty = none
