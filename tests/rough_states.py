@@ -21,16 +21,22 @@ every primitive field into every arm:
 Every state is a function of the global grid alone (seeded
 ``torch.Generator``), so engines of any layout, rank count and precision get
 the same field: build it once with ``global_state`` and ``install`` it.
+
+``fp32_twin_bound`` is the reference of every fp32 kernel test: the fp64
+oracle from the fp32-rounded state, and the increment error the PyTorch
+backend makes against it when it runs in fp32 from that same state.
 """
+import collections
 import functools
 
 import numpy as np
 import torch
 
-from stsphere.engine import assemble_global
+from stsphere.engine import Engine, assemble_global
 from stsphere.models.base import PPM, cells_x, cells_y, extend
 from stsphere.models.geometry import CubedSphereGrid
 from stsphere.models.swe import ShallowWater
+from stsphere.parallel.layout import TileLayout
 
 SWE_CLASSES = ("rough", "plateau", "zero_mom")
 PATCH = (2, 3)            # plateau patch: 2 cells along x, 3 along y
@@ -301,3 +307,79 @@ def increment_error(ref, hip, q0: torch.Tensor, bound=None, block=None, what: st
                 f"worst cell: {_where(ref, f, int(t), int(j), int(i), block)}; increment reference "
                 f"{float(da[f, t, j, i]):.6e} kernel {float(db[f, t, j, i]):.6e}, max |increment| {float(scale[f]):.3e}")
     return errs
+
+
+# ---------------------------------------------------------------------------
+# the fp32 reference: oracle and PyTorch twin from the rounded state
+# ---------------------------------------------------------------------------
+
+EPS32 = float(torch.finfo(torch.float32).eps)
+FP32_CAP = 1e-4           # the bound of the fp32 state tests the increment tests stand beside: none may be looser
+Fp32Reference = collections.namedtuple("Fp32Reference", "ref q0 twin bound")
+
+
+def physics_of(kind: str, lim: int):
+    """``kind``: "adv", "diff", "topo" (tc5 over ``topography``) or a shallow-water case."""
+    from stsphere.models.advection import Advection
+    from stsphere.models.diffusion import Diffusion
+    if kind == "adv":
+        return Advection(limiter=lim)
+    if kind == "diff":
+        return Diffusion()
+    if kind == "topo":
+        return TopographySWE("tc5", limiter=lim)
+    return ShallowWater(kind, limiter=lim)
+
+
+@functools.lru_cache(maxsize=None)
+def global_state(kind: str, N: int, cls: str) -> torch.Tensor:
+    """The global start state of a class: a function of the case and the grid
+    alone (not of the limiter, the layout, the precision or the device)."""
+    phys = physics_of(kind, 2)
+    return make_state(Engine(phys, TileLayout(N, 1, 1, ng=phys.halo), grid=grid_of(N)), cls)
+
+
+def engine_of(kind, N, t, lim, cls, backend="torch", dtype=torch.float64, integ="ssprk3", block=None, dt=None,
+              rounded=False, device="cuda"):
+    """(one-rank engine with the class's state installed, q0).  ``rounded``:
+    the state rounded to fp32 first (the start of the fp32 comparisons)."""
+    phys = physics_of(kind, lim)
+    e = Engine(phys, TileLayout(N, t, 1, ng=phys.halo), grid=grid_of(N), dtype=dtype, device=device,
+               backend=backend, integrator=integ, block=block, dt=dt)
+    G = global_state(kind, N, cls)
+    return e, install(e, G.float().double() if rounded else G)
+
+
+def twin_bound(twin_errs):
+    """max(4 x twin, 4 eps32) per field: the margin the project gives an fp32
+    kernel over the PyTorch twin (tests/test_derived_gpu.py), room for another
+    order of operations and nothing else; 4 eps32 where the twin happens to be
+    exact.  No bound may exceed ``FP32_CAP``."""
+    bound = [max(4.0 * x, 4.0 * EPS32) for x in twin_errs]
+    assert max(bound) <= FP32_CAP, f"fp32 twin bound {bound} above the cap {FP32_CAP}: the twin itself is off"
+    return bound
+
+
+def fp32_reference(make, steps: int) -> Fp32Reference:
+    """``make(dtype, dt)`` -> (engine started from the fp32-rounded state, q0).
+    Steps the fp64 oracle and, with the oracle's dt, the same backend in fp32;
+    the code under test takes no part.  Neither engine is stepped again."""
+    ref, q0 = make(torch.float64, None)
+    ref.step(steps)
+    twin, _ = make(torch.float32, ref.dt)
+    twin.step(steps)
+    if ref.device.type == "cuda":
+        torch.cuda.synchronize()
+    errs = increment_error(ref, twin, q0, what="fp32 twin")
+    return Fp32Reference(ref, q0, errs, twin_bound(errs))
+
+
+@functools.lru_cache(maxsize=None)
+def fp32_twin_bound(kind, N, t, lim=2, cls="rough", integ="ssprk3", steps=2, device="cuda") -> Fp32Reference:
+    """(ref, q0, twin, bound) of one case, computed once and shared by every
+    kernel shape that runs it: the fp64 oracle after ``steps`` steps from the
+    fp32-rounded state of class ``cls``, that state as installed, the per-field
+    increment error of the PyTorch backend run in fp32 from it (with the
+    oracle's dt), and ``twin_bound`` of that error."""
+    return fp32_reference(lambda dtype, dt: engine_of(kind, N, t, lim, cls, dtype=dtype, integ=integ, dt=dt,
+                                                      rounded=True, device=device), steps)

@@ -13,7 +13,8 @@ import functools
 import pytest
 import torch
 
-from rough_states import TopographySWE, global_of, grid_of, increment_error, install, make_state
+from rough_states import (TopographySWE, fp32_twin_bound, global_of, grid_of, increment_error, install,
+                          make_state)
 from stsphere.engine import Engine, VirtualCluster
 from stsphere.models.advection import Advection
 from stsphere.models.diffusion import Diffusion
@@ -247,20 +248,9 @@ def test_remote_ghost_path_on_rough(ranks):
 
 
 # ---- fp32 ---------------------------------------------------------------------------------------
-def _fp32_twin_bound(N, t):
-    """4 x the increment error of the PyTorch backend run in fp32 on the same
-    fp32-rounded state, per field, against the fp64 oracle from that state
-    (the margin tests/test_derived_gpu.py gives its fp32 kernel over the twin)."""
-    ref, q0 = _reference("tc5", N, t, 2, "rough", rounded=True)
-    twin, _ = _engine("tc5", N, t, 2, "rough", dtype=torch.float32, dt=ref.dt, rounded=True)
-    twin.step(STEPS)
-    torch.cuda.synchronize()
-    return ref, q0, increment_error(ref, twin, q0, what="fp32 twin")
-
-
 @pytest.mark.parametrize("family,N,t", [("block", 24, 2), ("march", 24, 1), ("march3", 48, 1), ("fused", 32, 2)])
 def test_fp32_rough(family, N, t):
-    ref, q0, twin = _fp32_twin_bound(N, t)
+    ref, q0, twin, _ = fp32_twin_bound("tc5", N, t, 2, "rough", "ssprk3", STEPS)
     block = {"block": (16, 16), "march": (64, 8)}.get(family)
     hip, _ = _engine("tc5", N, t, 2, "rough", backend="hip", dtype=torch.float32, block=block, dt=ref.dt,
                      rounded=True)

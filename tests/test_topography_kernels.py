@@ -21,7 +21,8 @@ import math
 import pytest
 import torch
 
-from rough_states import TopographySWE, global_of, grid_of, increment_error, install, make_state
+from rough_states import (TopographySWE, fp32_twin_bound, global_of, grid_of, increment_error, install,
+                          make_state)
 from stsphere.engine import Engine, VirtualCluster
 from stsphere.models.swe import ShallowWater
 from stsphere.parallel.layout import TileLayout
@@ -427,24 +428,12 @@ def test_rest_stays_at_rest(family, N, t):
 
 
 # ---- fp32 ---------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _fp32_twin_bound(N, t):
-    """4 x the increment error of the PyTorch backend run in fp32 on the same
-    fp32-rounded state, per field, against the fp64 oracle from that state
-    (tests/test_rough_kernels.py::_fp32_twin_bound); nothing fixed in advance."""
-    ref, q0 = _reference(TC5, N, t, rounded=True)
-    twin, _ = _engine(TC5, N, t, dtype=torch.float32, dt=ref.dt, rounded=True)
-    twin.step(STEPS)
-    torch.cuda.synchronize()
-    return ref, q0, increment_error(ref, twin, q0, what="fp32 twin")
-
-
 @pytest.mark.parametrize("family,N,t", [("block", 24, 2), ("march", 24, 1), ("march-compact", 24, 1), ("march3", 48, 1),
                                         ("fused", 32, 2)])
 def test_fp32(monkeypatch, family, N, t):
     """``march`` runs the per-tile records (the fp32 default), ``march-compact``
     the compact geometry."""
-    ref, q0, twin = _fp32_twin_bound(N, t)
+    ref, q0, twin, _ = fp32_twin_bound("topo", N, t, 2, "rough", "ssprk3", STEPS)
     if family.startswith("march") and family != "march3":
         hip, _ = _march_engine(monkeypatch, True if family == "march-compact" else None, TC5, N, t, 8, dt=ref.dt,
                                dtype=torch.float32, rounded=True)

@@ -13,9 +13,15 @@ flux F_h both signs, so both upwind arms are taken; the noise takes the
 opposite-sign and steep arms of every limiter, the patch the zero-difference
 arm and, at its rim, a jump of up to 1.
 """
+import functools
+
 import torch
 
-from rough_states import _uniform, global_of, increment_error, install, swe_state   # noqa: F401
+from rough_states import (Fp32Reference, _uniform, fp32_reference, global_of, grid_of, increment_error,   # noqa: F401
+                          install, swe_state)
+from stsphere.engine import Engine
+from stsphere.models.swe import ShallowWaterTracers
+from stsphere.parallel.layout import TileLayout
 
 TRACER_SETS = {1: ["cap"], 2: ["cap", "cosine_bell"], 4: ["cap", "cosine_bell", "gradient", "constant"]}
 
@@ -41,3 +47,32 @@ def make_state(engines, cls: str, seed: int = 0) -> torch.Tensor:
     swe = swe_state(G0[:4], engines[0].grid.centers(), cls, seed)
     q = rough_mixing_ratios(G0.shape[0] - 4, G0.shape[-1], seed)
     return torch.cat([swe, swe[0] * q])
+
+
+# ---- the fp32 reference (rough_states.fp32_twin_bound for the tracer physics) ----
+def tracer_physics(nq: int, lim: int):
+    return ShallowWaterTracers("tc5", tracers=TRACER_SETS[nq], limiter=lim)
+
+
+@functools.lru_cache(maxsize=None)
+def global_state(nq: int, N: int, cls: str) -> torch.Tensor:
+    """The global start state [4 + nq, 6, N, N] of a class: a function of the
+    tracer count and the grid alone."""
+    return make_state(Engine(tracer_physics(nq, 2), TileLayout(N, 1, 1, ng=2), grid=grid_of(N)), cls)
+
+
+def engine_of(nq, N, t, lim, cls, backend="torch", dtype=torch.float64, integ="ssprk3", block=None, dt=None,
+              rounded=False, device="cuda"):
+    """(one-rank tracer engine with the class's state installed, q0)."""
+    e = Engine(tracer_physics(nq, lim), TileLayout(N, t, 1, ng=2), grid=grid_of(N), dtype=dtype, device=device,
+               backend=backend, integrator=integ, block=block, dt=dt)
+    G = global_state(nq, N, cls)
+    return e, install(e, G.float().double() if rounded else G)
+
+
+@functools.lru_cache(maxsize=None)
+def fp32_twin_bound(nq, N, t, lim=2, cls="rough", integ="ssprk3", steps=1, device="cuda") -> Fp32Reference:
+    """(ref, q0, twin, bound) per field (h, M, hq_k) of one tracer case: see
+    ``rough_states.fp32_twin_bound``."""
+    return fp32_reference(lambda dtype, dt: engine_of(nq, N, t, lim, cls, dtype=dtype, integ=integ, dt=dt,
+                                                      rounded=True, device=device), steps)
