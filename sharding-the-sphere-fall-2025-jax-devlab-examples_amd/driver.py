@@ -75,6 +75,14 @@ def make_physics(pc) -> Any:
                          f"not {tracers!r}")
     if tracers and model != "swe":
         raise ValueError(f"physics.tracers: tracers are carried by the shallow-water model, not {model!r}")
+    tlim = getattr(pc, "tracer_limiter", None)
+    if tlim is not None:
+        if not (isinstance(tlim, str) and tlim.lower() == "ppm"):
+            raise ValueError(f"physics.tracer_limiter: null or ppm expected, not {tlim!r}")
+        if not tracers:
+            raise ValueError("physics.tracer_limiter: set together with physics.tracers (it reconstructs the "
+                             "mixing ratios)")
+        tlim = "ppm"
     op = pc.operator
     if op not in OPERATORS:
         raise ValueError(f"physics.operator: one of {list(OPERATORS)} expected, not {op!r}")
@@ -82,7 +90,7 @@ def make_physics(pc) -> Any:
         raise ValueError(f"physics.operator: consistent is defined for the diffusion model, not {model!r}")
     if model == "swe":
         if tracers:
-            return ShallowWaterTracers(case, tracers=list(tracers), limiter=lim, alpha=pc.alpha)
+            return ShallowWaterTracers(case, tracers=list(tracers), limiter=lim, alpha=pc.alpha, tracer_limiter=tlim)
         return ShallowWater(case, limiter=lim, alpha=pc.alpha)
     if model == "advection":
         return Advection(case, alpha=pc.alpha, limiter=lim)
@@ -467,6 +475,22 @@ class Solver(SolverDiagnostics):
         if ht is None:
             return None
         return williamson_norms(h, ht, self.grid.areas())
+
+    def tracer_error_norms(self, k: int = 0) -> Optional[Dict[str, float]]:
+        """Williamson l1 / l2 / linf of the mixing ratio q_k against its true
+        solution at the current time (a ``cosine_bell`` tracer on TC2), on
+        rank 0; None where there is no closed form (and on other ranks)."""
+        from .models.errors import williamson_norms
+        exact = getattr(self.physics, "tracer_exact", None)
+        if exact is None:
+            return None
+        qt = exact(self.grid, self.time, int(k))     # the same answer on every rank: the gather below is collective
+        if qt is None:
+            return None
+        q = self.tracer(k)
+        if q is None:
+            return None
+        return williamson_norms(q, qt, self.grid.areas())
 
     def all_finite(self) -> bool:
         if self.runner is not None:
@@ -907,6 +931,10 @@ class Solver(SolverDiagnostics):
         norms = self.error_norms()
         if norms is not None:
             summary.update({f"err_{k}": v for k, v in norms.items()})
+        for j in range(getattr(self.physics, "nq", 0)):
+            tn = self.tracer_error_norms(j)
+            if tn is not None:
+                summary.update({f"tracer{j}_err_{k}": v for k, v in tn.items()})
         self._log(f"Run complete: {done} steps, {summary['sim_days']:.3f} days, "
                   f"{summary['cell_updates_per_s']:.3e} cell-updates/s (setup {summary['setup_s']:.3f} s excluded)")
         return summary

@@ -262,7 +262,12 @@ def limited_slope(dl: torch.Tensor, dr: torch.Tensor, lim: int) -> torch.Tensor:
     raise ValueError(lim)
 
 
-def ppm_faces(q: torch.Tensor, g: int, n: int, lo_edge=None, hi_edge=None):
+def clamp_between(a: torch.Tensor, l: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+    """a confined to [min(l, r), max(l, r)]."""
+    return torch.minimum(torch.maximum(a, torch.minimum(l, r)), torch.maximum(l, r))
+
+
+def ppm_faces(q: torch.Tensor, g: int, n: int, lo_edge=None, hi_edge=None, monotone: bool = False):
     """PPM face values of cells -1..n of each row (q: [..., W], cell c at index
     c + g, g >= 3).  Fourth-order interface values
     a_{k-1/2} = 7/12 (q_{k-1} + q_k) - 1/12 (q_{k-2} + q_{k+1}), then the
@@ -273,11 +278,17 @@ def ppm_faces(q: torch.Tensor, g: int, n: int, lo_edge=None, hi_edge=None):
     drops to first order there (measured on TC2).  Cells whose stencil crosses
     a panel edge (lo_edge / hi_edge: bool, broadcastable to q[..., :1], true
     where the row's low / high end is a panel edge) therefore use the MC-limited
-    PLR faces instead, the usual second-order edge treatment."""
+    PLR faces instead, the usual second-order edge treatment.
+
+    ``monotone``: every interface value is first confined between its two
+    cells (the fourth-order value is not, and the parabola limiter alone does
+    not repair that: a 0/1 cap then leaves [0, 1]); the tracers' scheme."""
     def cell(c0, c1):          # cells c0..c1-1
         return q[..., c0 + g:c1 + g]
     # interfaces k - 1/2 for k = -1 .. n + 1 (between cells k - 1 and k)
     a = (7.0 / 12.0) * (cell(-2, n + 1) + cell(-1, n + 2)) - (1.0 / 12.0) * (cell(-3, n) + cell(0, n + 3))
+    if monotone:
+        a = clamp_between(a, cell(-2, n + 1), cell(-1, n + 2))
     aL, aR = a[..., :-1], a[..., 1:]
     qc = cell(-1, n + 1)
     aL2, aR2 = ppm_limit(qc, aL, aR)
@@ -294,7 +305,8 @@ def ppm_faces(q: torch.Tensor, g: int, n: int, lo_edge=None, hi_edge=None):
     return aL2, aR2
 
 
-def plr_x(qe: torch.Tensor, g: int, n: int, lim: int, pedge: Optional[torch.Tensor] = None):
+def plr_x(qe: torch.Tensor, g: int, n: int, lim: int, pedge: Optional[torch.Tensor] = None,
+          monotone: bool = False):
     """Left/right PLR (or PPM, lim = 4) states at the n+1 x-edges of the
     interior rows: returns (qL, qR) each [..., n, n+1].  qe: [..., T, W, W];
     pedge: [T] panel-edge side bits (RankGeometry.pedge), used by PPM."""
@@ -306,7 +318,7 @@ def plr_x(qe: torch.Tensor, g: int, n: int, lim: int, pedge: Optional[torch.Tens
         if pedge is not None:
             lo = ((pedge & 1) != 0)[:, None, None]
             hi = ((pedge & 2) != 0)[:, None, None]
-        aL, aR = ppm_faces(rows, g, n, lo, hi)    # cells -1..n
+        aL, aR = ppm_faces(rows, g, n, lo, hi, monotone)    # cells -1..n
         return aR[..., :-1], aL[..., 1:]
     d = rows[..., 1:] - rows[..., :-1]
     s = limited_slope(d[..., g - 2:g + n], d[..., g - 1:g + n + 1], lim)
@@ -314,10 +326,11 @@ def plr_x(qe: torch.Tensor, g: int, n: int, lim: int, pedge: Optional[torch.Tens
     return (c + 0.5 * s)[..., :-1], (c - 0.5 * s)[..., 1:]
 
 
-def plr_y(qe: torch.Tensor, g: int, n: int, lim: int, pedge: Optional[torch.Tensor] = None):
+def plr_y(qe: torch.Tensor, g: int, n: int, lim: int, pedge: Optional[torch.Tensor] = None,
+          monotone: bool = False):
     """(qL, qR) each [..., n+1, n] at the y-edges of the interior columns."""
     pe = None if pedge is None else (pedge >> 2)      # S, N bits -> low, high
-    qL, qR = plr_x(qe.transpose(-1, -2), g, n, lim, pe)
+    qL, qR = plr_x(qe.transpose(-1, -2), g, n, lim, pe, monotone)
     return qL.transpose(-1, -2), qR.transpose(-1, -2)
 
 
@@ -379,20 +392,25 @@ def ppm_limit(qc, aL, aR):
     return aL2, aR2
 
 
-def _inner_face(line, lim: int):
+def _inner_face(line, lim: int, monotone: bool = False):
     """Face value, on the side of index g - 1, of the cell at index g of a
-    1-D line [..., 2g] (cells g-1, g-2, ... are on the other panel)."""
+    1-D line [..., 2g] (cells g-1, g-2, ... are on the other panel).
+    ``monotone``: PPM interface values confined between their cells
+    (``ppm_faces``)."""
     g = line.shape[-1] // 2
     c, l, r = line[..., g], line[..., g - 1], line[..., g + 1]
     if lim == PPM:
         l2, r2 = line[..., g - 2], line[..., g + 2]
         aL = (7.0 / 12.0) * (l + c) - (1.0 / 12.0) * (l2 + r)
         aR = (7.0 / 12.0) * (c + r) - (1.0 / 12.0) * (l + r2)
+        if monotone:
+            aL, aR = clamp_between(aL, l, c), clamp_between(aR, c, r)
         return ppm_limit(c, aL, aR)[0]
     return c - 0.5 * limited_slope(c - l, r - c, lim)
 
 
-def reconstruct(w: torch.Tensor, tens: Dict[str, torch.Tensor], g: int, n: int, lim: int):
+def reconstruct(w: torch.Tensor, tens: Dict[str, torch.Tensor], g: int, n: int, lim: int,
+                monotone: bool = False):
     """Edge states of the interior x- and y-edges with the panel-edge
     treatment.  w: window [F, T, W, W] with raw (index-space copy) ghosts.
 
@@ -406,13 +424,16 @@ def reconstruct(w: torch.Tensor, tens: Dict[str, torch.Tensor], g: int, n: int, 
       their common edge, so the flux is single-valued (conservative).
     * The cell values returned for wave-speed estimates are real cells on both
       sides of every edge.
+    * ``monotone`` (PPM only): the interface values, the neighbour's included,
+      are confined between their two cells before the parabola limiter
+      (``ppm_faces``); off, nothing changes by a bit.
 
     Returns (xL, xR, cxL, cxR) at the x-edges [F,T,n,n+1] and (yL, yR, cyL, cyR)
     at the y-edges [F,T,n+1,n]."""
     pe = tens.get("pedge")
     if pe is None or "pe_base" not in tens:
-        xL, xR = plr_x(w, g, n, lim, pe)
-        yL, yR = plr_y(w, g, n, lim, pe)
+        xL, xR = plr_x(w, g, n, lim, pe, monotone)
+        yL, yR = plr_y(w, g, n, lim, pe, monotone)
         return (xL, xR) + cells_x(w, g, n), (yL, yR) + cells_y(w, g, n)
     base, frac = tens["pe_base"], tens["pe_t"]
     wi = w.clone()
@@ -432,9 +453,9 @@ def reconstruct(w: torch.Tensor, tens: Dict[str, torch.Tensor], g: int, n: int, 
             _strip(wi, side, k, g, n).copy_(torch.where(mk, _interp(_strip_ext(w, side, k, g, n), b, t), x))
             gp.append(_interp(_own_ext(w, side, k, g, n), b, t))
         line = torch.stack(gp[::-1] + raw, -1)              # [F,T,n,2g]
-        faces[side] = (m, _inner_face(line, lim), raw[0])
-    xL, xR = plr_x(wi, g, n, lim)
-    yL, yR = plr_y(wi, g, n, lim)
+        faces[side] = (m, _inner_face(line, lim, monotone), raw[0])
+    xL, xR = plr_x(wi, g, n, lim, monotone=monotone)
+    yL, yR = plr_y(wi, g, n, lim, monotone=monotone)
     cxL, cxR = cells_x(w, g, n)
     cyL, cyR = cells_y(w, g, n)
     for side, (m, fv, r0) in faces.items():

@@ -196,11 +196,24 @@ class ShallowWaterTracers(ShallowWater):
     parent's order: bit-identical to ``ShallowWater``.
 
     ``tracers``: initial conditions, names of ``initial_conditions.tracer_field``
-    (or numbers: a constant mixing ratio).  PLR limiters only."""
+    (or numbers: a constant mixing ratio).  PLR limiters only for (h, v).
+
+    ``tracer_limiter``: None (the mixing ratios use ``limiter``) or "ppm" / 4:
+    the mixing ratios alone are reconstructed by the monotone PPM
+    (``base.ppm_faces(..., monotone=True)``: interface values confined between
+    their two cells, then the Colella-Woodward limiter) on a three-layer window,
+    while (h, v) keep ``limiter``; (h, M) stay bit-for-bit those of a plain
+    run."""
     kernel_id = 3
 
-    def __init__(self, case: str = "tc5", tracers=("cap",), **kw):
+    def __init__(self, case: str = "tc5", tracers=("cap",), tracer_limiter=None, **kw):
         super().__init__(case, **kw)
+        if tracer_limiter in ("ppm", PPM):
+            self.tracer_limiter = PPM
+        elif tracer_limiter is None:
+            self.tracer_limiter = None
+        else:
+            raise ValueError(f"shallow water with tracers: tracer_limiter is None or 'ppm', got {tracer_limiter!r}")
         tracers = list(tracers)
         if not 1 <= len(tracers) <= MAX_TRACERS:
             raise ValueError(f"shallow water with tracers: 1 to {MAX_TRACERS} tracers, got {len(tracers)}")
@@ -224,14 +237,33 @@ class ShallowWaterTracers(ShallowWater):
         q = self.tracer_fields(geo.grid)
         return np.concatenate([q4] + [(q4[0] * geo.gather_global(q[k]))[None] for k in range(self.nq)], 0)
 
+    @property
+    def halo(self) -> int:
+        return 3 if self.tracer_limiter == PPM else recon_halo(self.limiter)
+
     def kernel_params(self):
-        return dict(super().kernel_params(), nq=self.nq)
+        return dict(super().kernel_params(), nq=self.nq, tracer_limiter=self.tracer_limiter or 0)
+
+    def tracer_exact(self, grid: CubedSphereGrid, t: float, k: int):
+        """True mixing ratio q_k(t) [6, N, N] where it has a closed form: a
+        ``cosine_bell`` on TC2, whose wind is TC1's solid-body rotation, is the
+        rotated bell; else None."""
+        if not 0 <= int(k) < self.nq:
+            raise ValueError(f"tracer_exact({k}): this physics carries {self.nq} tracer(s)")
+        if self.case == "tc2" and self.tracers[int(k)] == "cosine_bell":
+            return ic.cosine_bell_exact(grid.centers(), t, self.alpha, radius=grid.radius, h0=1.0)
+        return None
 
     def rhs(self, qe, qi, tens, n, g):
         h = qe[0]
         safe = torch.where(h != 0, h, torch.ones_like(h))
         w = torch.cat([h[None], qe[1:] / safe])                      # h, v, q_k (0 where h = 0)
-        (wL, wR, cL, cR), (yL, yR, dL, dR) = reconstruct(w, tens, g, n, self.limiter)
+        if self.tracer_limiter == PPM:    # (h, v): the parent's call; q_k: monotone PPM on the same window
+            (wL, wR, cL, cR), (yL, yR, dL, dR) = reconstruct(w[:4], tens, g, n, self.limiter)
+            (tL, tR, _, _), (uL, uR, _, _) = reconstruct(w[4:], tens, g, n, PPM, monotone=True)
+            wL, wR, yL, yR = torch.cat([wL, tL]), torch.cat([wR, tR]), torch.cat([yL, uL]), torch.cat([yR, uR])
+        else:
+            (wL, wR, cL, cR), (yL, yR, dL, dR) = reconstruct(w, tens, g, n, self.limiter)
         mx = tens["mx"].permute(1, 0, 2)[:, :, None, :]
         Fx = self._flux(wL[:4], wR[:4], cL[:4], cR[:4], mx, tens["ex"])
         my = tens["my"].permute(1, 0, 2)[:, :, :, None]

@@ -72,6 +72,8 @@ typedef struct StageDesc {
                         // rank, < -1 remote code (as push), -1 none (nullable)
   int nq;               // shallow water with tracers (phys 3, swe_tracer_stage.hip): tracer fields, 1 .. 4;
                         // the state then holds F = 4 + nq fields (h, M, hq_k) and recv is [R][4 + nq]
+  int tracer_limiter;   // phys 3: reconstruction of the mixing ratios, 0 = as `limiter`, 4 = monotone PPM
+                        // (interface values confined between their cells; needs mg >= 3)
 } StageDesc;
 
 int stsp_stage_launch(int phys, int dtype, int bx, int by, const StageDesc* d, hipStream_t stream);

@@ -17,24 +17,38 @@
 // Push map, carried corner ghosts (cpush / cgmap), partial blocks and the
 // block_sides rule are those of stage_kernel.hip.  No xGMI, no stamps.
 //
-// NQ is a launch argument, not a template parameter (48 instantiations: fp64 /
-// fp32, 16x16 / 16x8, limiters 0-3, plain / block list / block list + remote
-// ghosts).  LDS is dynamic, sized by NQ (TrGeom::elems), AND the flux array is
-// reused: it holds F_h, F_M and the flux of tracer 0 (5 rows); tracers 1 .. 3
-// wait in registers and go through rows 1 .. 3 in a second pass once the
-// momentum fluxes are consumed.  16x16 fp64 with NQ = 4: 63 824 bytes, under the
-// 64 KiB a launch gets without opting in.
+// TLIM, the tracers' reconstruction, is "same as LIM" (0) or the monotone PPM
+// (4, ShallowWaterTracers(tracer_limiter="ppm")): the mixing ratios alone go
+// through PPM whose interface values are confined between their two cells
+// before the Colella-Woodward limiter, (h, v) keep LIM.  The window then has
+// three ghost layers (NG is a template value), the tracer faces are formed in
+// the flux phase from six window cells per edge (no face arrays in LDS), and
+// the panel-edge fix-up interpolates ghost layers 0 and 1 of the tracer rows
+// (layer 0 only of the SWE rows) and builds the neighbour's tracer edge state
+// on the six-cell line of models/base.py::_inner_face.
+//
+// NQ is a launch argument, not a template parameter (96 instantiations: fp64 /
+// fp32, 16x16 / 16x8, limiters 0-3, tracers as LIM / PPM, plain / block list /
+// block list + remote ghosts).  LDS is dynamic, sized by NQ (TrGeom::elems), AND
+// the flux array is reused: it holds F_h, F_M and the flux of tracer 0 (5 rows);
+// tracers 1 .. 3 wait in registers and go through rows 1 .. 3 in a second pass
+// once the momentum fluxes are consumed.  16x16 fp64 with NQ = 4: 63 824 bytes,
+// under the 64 KiB a launch gets without opting in; with PPM tracers 70 016
+// bytes, which the launcher refuses (NQ <= 3: 65 456; 16x8 with NQ = 4: 43 904).
 #include "stage_common.h"
 
 namespace {
 
-constexpr int TR_NG = 2;      // ghost layers (PLR)
 constexpr int TR_MAXQ = 4;
+constexpr int TR_PPM = 4;     // TLIM: monotone PPM for the mixing ratios (0: same as LIM)
+constexpr int tr_ng(int tlim) { return tlim == TR_PPM ? 3 : 2; }   // ghost layers
 
-template <int BX, int BY> struct TrGeom {
+// NG ghost layers; the fix-up interpolates layer 0 of every field and, with
+// NG = 3, layer 1 of the tracer rows
+template <int BX, int BY, int NG> struct TrGeom {
   static constexpr int NX = (BX + 1) * BY, NY = BX * (BY + 1), NE = NX + NY;
   static constexpr int NT = ((NE + 63) / 64) * 64;
-  static constexpr int EX = BX + 2 * TR_NG, EY = BY + 2 * TR_NG;
+  static constexpr int EX = BX + 2 * NG, EY = BY + 2 * NG;
   static constexpr int WS = EX + 1, WF = EY * WS;      // window row / field stride
   static constexpr int BM = BX > BY ? BX : BY, EM = EX > EY ? EX : EY;
   static constexpr int NB = BX + BY + 2;               // normals: x columns, then y rows
@@ -45,13 +59,37 @@ template <int BX, int BY> struct TrGeom {
   }
   static_assert(EX * EY <= NT, "one window cell per thread");
   static_assert(3 * NB <= NT, "one normal component per thread");
-  static_assert(4 * (4 + TR_MAXQ) * EM <= FLR * NE, "the raw strip copy fits in the flux array");
+  // raw strip copy: layer 0 of all 4 + NQ fields, layer 1 of the NQ tracer rows (NG = 3)
+  static constexpr int raw_rows(int nq) { return 4 + nq + (NG == 3 ? nq : 0); }
+  static_assert(4 * raw_rows(TR_MAXQ) * EM <= FLR * NE, "the raw strip copy fits in the flux array");
 };
 
-template <typename T, int BX, int BY, int LIM, bool REMOTE, bool LIST>
-__global__ __launch_bounds__((TrGeom<BX, BY>::NT)) void swe_tracer_kernel(Args<T> a, const int NQ) {
-  using G = TrGeom<BX, BY>;
-  constexpr int NG = TR_NG, NT = G::NT, NX = G::NX, NY = G::NY, NE = G::NE;
+// monotone PPM (models/base.py::ppm_faces, monotone): the fourth-order interface
+// value between cells b and c of the line a b | c d, confined to [min, max](b, c)
+template <typename T>
+__device__ __forceinline__ T ppm_iface(T a, T b, T c, T d) {
+  const T v = T(7.0 / 12.0) * (b + c) - T(1.0 / 12.0) * (a + d);
+  return tmin(tmax(v, tmin(b, c)), tmax(b, c));
+}
+// Colella-Woodward monotonicity limiter of one cell (models/base.py::ppm_limit)
+template <typename T>
+__device__ __forceinline__ void ppm_limit(T c0, T aL, T aR, T& nL, T& nR) {
+  const bool flat = (aR - c0) * (c0 - aL) <= T(0);
+  const T d = aR - aL;
+  const T m6 = T(6) * (c0 - T(0.5) * (aL + aR));
+  const bool ovl = d * m6 > d * d;
+  const bool ovr = -(d * d) > d * m6;
+  nL = flat ? c0 : (ovl ? T(3) * c0 - T(2) * aR : aL);
+  nR = flat ? c0 : ((!ovl && ovr) ? T(3) * c0 - T(2) * aL : aR);
+}
+
+template <typename T, int BX, int BY, int LIM, int TLIM, bool REMOTE, bool LIST>
+__global__ __launch_bounds__((TrGeom<BX, BY, tr_ng(TLIM)>::NT)) void swe_tracer_kernel(Args<T> a, const int NQ) {
+  constexpr int NG = tr_ng(TLIM);
+  constexpr bool TPPM = TLIM == TR_PPM;
+  constexpr int KG = TPPM ? 2 : 1;                // interpolated ghost layers (tracer rows)
+  using G = TrGeom<BX, BY, NG>;
+  constexpr int NT = G::NT, NX = G::NX, NY = G::NY, NE = G::NE;
   constexpr int EX = G::EX, EY = G::EY, WS = G::WS, WF = G::WF, BM = G::BM, EM = G::EM;
   extern __shared__ __align__(16) unsigned char tr_smem[];
   const int FR = 4 + NQ;                          // reconstructed fields = state fields
@@ -61,7 +99,10 @@ __global__ __launch_bounds__((TrGeom<BX, BY>::NT)) void swe_tracer_kernel(Args<T
   T* const s_pr = s_pf + FR * 4 * BM;             // [5][4 BM] neighbour's raw cell (h, v, c)
   T* const s_nrm = s_pr + 5 * 4 * BM;             // [3][NB]
   T* const s_len = s_nrm + 3 * G::NB;             // [NE]
-  T* const s_raw = s_fl;                          // [4][FR][EM] raw ghost layer 0 (until the flux phase)
+  // raw ghosts (until the flux phase): [4][RR][EM], rows f < FR layer 0 of field
+  // f, rows FR + k layer 1 of tracer k (PPM)
+  T* const s_raw = s_fl;
+  const int RR = FR + (KG - 1) * NQ;
   auto wfield = [](int f) { return f < 4 ? f : f + 1; };   // window row of reconstructed field f
 
   const int bid = LIST ? a.blocks[blockIdx.x] : xcd_remap(blockIdx.x, a.nblocks);
@@ -221,13 +262,19 @@ __global__ __launch_bounds__((TrGeom<BX, BY>::NT)) void swe_tracer_kernel(Args<T
       int side = -1, k = 0, al = 0;
       if (!inx) {
         side = x < 0 ? 0 : 1; k = x < 0 ? -1 - x : x - n; al = ly;
-        if (!(k < 1 && ((bsides >> side) & 1))) side = -1;
+        if (!(k < KG && ((bsides >> side) & 1))) side = -1;
       }
       if (side < 0 && !iny) { side = y < 0 ? 2 : 3; k = y < 0 ? -1 - y : y - n; al = lx; }
-      if (side >= 0 && k < 1 && ((bsides >> side) & 1) && !(inx && iny)) {
+      if (side >= 0 && k < KG && ((bsides >> side) & 1) && !(inx && iny)) {
+        if (!TPPM || k == 0) {
 #pragma unroll
-        for (int f = 0; f < 4 + TR_MAXQ; ++f)
-          if (f < FR) s_raw[(side * FR + f) * EM + al] = w[f];
+          for (int f = 0; f < 4 + TR_MAXQ; ++f)
+            if (f < FR) s_raw[(side * RR + f) * EM + al] = w[f];
+        } else {
+#pragma unroll
+          for (int q = 0; q < TR_MAXQ; ++q)
+            if (q < NQ) s_raw[(side * RR + FR + q) * EM + al] = w[4 + q];
+        }
       }
     }
   } else {
@@ -254,17 +301,43 @@ __global__ __launch_bounds__((TrGeom<BX, BY>::NT)) void swe_tracer_kernel(Args<T
       };
       const int pab = (pside < 2 ? y0 : x0) - NG;            // tile-local coordinate of window position 0
       T* const wf = s_w + wfield(f) * WF;
-      const T* const raw = s_raw + (pside * FR + f) * EM;
+      const T* const raw = s_raw + (pside * RR + f) * EM;
       const T g0 = raw[pb - pab], g1 = raw[pb + 1 - pab];
       const T gk = g0 + ptt * (g1 - g0);
       const int co = plow ? 0 : n - 1;
       const T o0 = wf[widx(co, pb)], o1 = wf[widx(co, pb + 1)];
       const T l = o0 + ptt * (o1 - o0);
       const T c = raw[pj - pab];
-      const T r = wf[widx(plow ? -2 : n + 1, pj)];
-      const T nf = c - half_slope<LIM>(c - l, r - c);
       const int wend = (pside < 2 ? x0 + BX : y0 + BY) + NG;   // first coordinate past the window
+      // PPM: the block that holds the panel edge itself uses the neighbour's
+      // state; a block whose window merely reaches the strip (NG cells short of
+      // the edge) only needs the ghosts, and its window ends before raw layer 2
+      const bool pown = !TPPM || plow || n + NG <= wend;
+      T nf = T(0);
+      if (TPPM && f >= 4) {
+        // layer 1 with its own pair; the neighbour's face on the line
+        // [gp1, gp0 | raw0, raw1, raw2] (gp2 is not read)
+        const int pb1 = a.pe_base[ti + n];
+        const T pt1 = a.pe_t[ti + n];
+        const T* const raw1 = s_raw + (pside * RR + FR + (f - 4)) * EM;
+        const T h0 = raw1[pb1 - pab], h1 = raw1[pb1 + 1 - pab];
+        const T gk1 = h0 + pt1 * (h1 - h0);
+        if (pown) {
+          const int co1 = plow ? 1 : n - 2;
+          const T u0 = wf[widx(co1, pb1)], u1 = wf[widx(co1, pb1 + 1)];
+          const T l2 = u0 + pt1 * (u1 - u0);
+          const T r = raw1[pj - pab];
+          const T r2 = wf[widx(plow ? -3 : n + 2, pj)];
+          T nR;
+          ppm_limit<T>(c, ppm_iface<T>(l2, l, c, r), ppm_iface<T>(l, c, r, r2), nf, nR);
+        }
+        if (plow || n + 1 < wend) wf[widx(plow ? -2 : n + 1, pj)] = gk1;
+      } else if (pown) {
+        const T r = wf[widx(plow ? -2 : n + 1, pj)];
+        nf = c - half_slope<LIM>(c - l, r - c);
+      }
       if (plow || n < wend) wf[widx(plow ? -1 : n, pj)] = gk;
+      if (!pown) continue;
       const int pslt = pside * BM + pjl;
       s_pf[f * 4 * BM + pslt] = nf;
       if (f < 4) s_pr[f * 4 * BM + pslt] = c;
@@ -318,9 +391,21 @@ __global__ __launch_bounds__((TrGeom<BX, BY>::NT)) void swe_tracer_kernel(Args<T
       if (k < NQ) {
         const T* wq = s_w + (5 + k) * WF;
         const T m1 = wq[cl_ - cst], c0 = wq[cl_], p1 = wq[cl_ + cst], p2 = wq[cl_ + 2 * cst];
-        const T d1 = p1 - c0;
-        T ql = c0 + half_slope<LIM>(c0 - m1, d1);
-        T qr = p1 - half_slope<LIM>(d1, p2 - p1);
+        T ql, qr;
+        if constexpr (TPPM) {
+          // the three interfaces around the left and the right cell, then aR of
+          // the left and aL of the right cell
+          const T m2 = wq[cl_ - 2 * cst], p3 = wq[cl_ + 3 * cst];
+          const T ia = ppm_iface<T>(m2, m1, c0, p1), ib = ppm_iface<T>(m1, c0, p1, p2);
+          const T ic = ppm_iface<T>(c0, p1, p2, p3);
+          T dum;
+          ppm_limit<T>(c0, ia, ib, dum, ql);
+          ppm_limit<T>(p1, ib, ic, qr, dum);
+        } else {
+          const T d1 = p1 - c0;
+          ql = c0 + half_slope<LIM>(c0 - m1, d1);
+          qr = p1 - half_slope<LIM>(d1, p2 - p1);
+        }
         if (pslot >= 0) {
           const T pv = s_pf[(4 + k) * 4 * BM + pslot];
           if (plo) ql = pv; else qr = pv;
@@ -450,46 +535,49 @@ __global__ __launch_bounds__((TrGeom<BX, BY>::NT)) void swe_tracer_kernel(Args<T
   }
 }
 
-template <typename T, int BX, int BY, int LIM>
+template <typename T, int BX, int BY, int LIM, int TLIM>
 int tr_launch_l(const StageDesc* d, hipStream_t s) {
-  using G = TrGeom<BX, BY>;
+  using G = TrGeom<BX, BY, tr_ng(TLIM)>;
   const Args<T> a = make_args<T>(d);
   const int nq = d->nq;
   const size_t lds = (size_t)G::elems(nq) * sizeof(T);
   if (lds > 65536) return -13;
   const dim3 grid(d->nblocks), block(G::NT);
   if (d->remote)
-    hipLaunchKernelGGL((swe_tracer_kernel<T, BX, BY, LIM, true, true>), grid, block, lds, s, a, nq);
+    hipLaunchKernelGGL((swe_tracer_kernel<T, BX, BY, LIM, TLIM, true, true>), grid, block, lds, s, a, nq);
   else if (d->blocks)
-    hipLaunchKernelGGL((swe_tracer_kernel<T, BX, BY, LIM, false, true>), grid, block, lds, s, a, nq);
+    hipLaunchKernelGGL((swe_tracer_kernel<T, BX, BY, LIM, TLIM, false, true>), grid, block, lds, s, a, nq);
   else
-    hipLaunchKernelGGL((swe_tracer_kernel<T, BX, BY, LIM, false, false>), grid, block, lds, s, a, nq);
+    hipLaunchKernelGGL((swe_tracer_kernel<T, BX, BY, LIM, TLIM, false, false>), grid, block, lds, s, a, nq);
   return (int)hipGetLastError();
 }
 
-template <typename T, int BX, int BY>
+template <typename T, int BX, int BY, int TLIM>
 int tr_launch_t(const StageDesc* d, hipStream_t s) {
   if (d->nblocks <= 0) return 0;
   if (d->nq < 1 || d->nq > TR_MAXQ) return -14;
-  if (d->pw != d->n + 2 * d->mg || d->mg < TR_NG) return -5;
+  if (d->pw != d->n + 2 * d->mg || d->mg < 2) return -5;
+  if (d->mg < tr_ng(TLIM)) return -15;                                 // PPM tracers: three ghost layers
   if (!d->pedge || !d->pe_base || !d->pe_t || d->n < 2) return -12;   // panel-edge tables
   if (!d->mx || !d->my || !d->cgeo || !d->ex || !d->ey) return -6;
   if (!d->push || (d->remote && (!d->gmap || !d->blocks || !d->recv))) return -6;
   if (d->xg) return -10;                                               // no direct xGMI halo
   switch (d->limiter) {
-    case 0: return tr_launch_l<T, BX, BY, 0>(d, s);
-    case 1: return tr_launch_l<T, BX, BY, 1>(d, s);
-    case 2: return tr_launch_l<T, BX, BY, 2>(d, s);
-    case 3: return tr_launch_l<T, BX, BY, 3>(d, s);
-    case 4: return -11;                                                // PPM: not with tracers
+    case 0: return tr_launch_l<T, BX, BY, 0, TLIM>(d, s);
+    case 1: return tr_launch_l<T, BX, BY, 1, TLIM>(d, s);
+    case 2: return tr_launch_l<T, BX, BY, 2, TLIM>(d, s);
+    case 3: return tr_launch_l<T, BX, BY, 3, TLIM>(d, s);
+    case 4: return -11;                                                // PPM for (h, v): not with tracers
   }
   return -7;
 }
 
 template <typename T>
 int tr_launch_p(int bx, int by, const StageDesc* d, hipStream_t s) {
-  if (bx == 16 && by == 16) return tr_launch_t<T, 16, 16>(d, s);
-  if (bx == 16 && by == 8) return tr_launch_t<T, 16, 8>(d, s);
+  if (d->tracer_limiter != 0 && d->tracer_limiter != TR_PPM) return -16;
+  const bool ppm = d->tracer_limiter == TR_PPM;
+  if (bx == 16 && by == 16) return ppm ? tr_launch_t<T, 16, 16, TR_PPM>(d, s) : tr_launch_t<T, 16, 16, 0>(d, s);
+  if (bx == 16 && by == 8) return ppm ? tr_launch_t<T, 16, 8, TR_PPM>(d, s) : tr_launch_t<T, 16, 8, 0>(d, s);
   return -2;
 }
 
@@ -504,7 +592,18 @@ extern "C" int stsp_swe_tracer_launch(int dtype, int bx, int by, const StageDesc
 // dynamic LDS bytes of a launch (host-side contract check)
 extern "C" int stsp_swe_tracer_lds(int dtype, int bx, int by, int nq) {
   const int es = dtype == 1 ? 8 : 4;
-  if (bx == 16 && by == 16) return TrGeom<16, 16>::elems(nq) * es;
-  if (bx == 16 && by == 8) return TrGeom<16, 8>::elems(nq) * es;
+  if (bx == 16 && by == 16) return TrGeom<16, 16, 2>::elems(nq) * es;
+  if (bx == 16 && by == 8) return TrGeom<16, 8, 2>::elems(nq) * es;
+  return -1;
+}
+
+// the same for a tracer reconstruction (0: as the limiter, 4: monotone PPM on a
+// three-layer window); a launch over 65536 bytes is refused with -13
+extern "C" int stsp_swe_tracer_lds_tl(int dtype, int bx, int by, int nq, int tracer_limiter) {
+  if (tracer_limiter == 0) return stsp_swe_tracer_lds(dtype, bx, by, nq);
+  if (tracer_limiter != TR_PPM) return -1;
+  const int es = dtype == 1 ? 8 : 4;
+  if (bx == 16 && by == 16) return TrGeom<16, 16, 3>::elems(nq) * es;
+  if (bx == 16 && by == 8) return TrGeom<16, 8, 3>::elems(nq) * es;
   return -1;
 }

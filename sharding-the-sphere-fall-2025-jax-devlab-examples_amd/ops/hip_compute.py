@@ -164,14 +164,33 @@ def choose_block(n: int, tiles: int = 0, cus: int = 0, limiter: int = 0, esize: 
     return best
 
 
-def choose_tracer_block(n: int, tiles: int = 0, cus: int = 0):
+TRACER_LDS_MAX = 65536    # dynamic LDS a launch gets without opting in
+
+
+def tracer_lds_bytes(bx: int, by: int, nq: int, esize: int = 8, tracer_limiter: int = 0) -> int:
+    """Dynamic LDS of one tracer stage block (swe_tracer_stage.hip,
+    ``TrGeom::elems(nq) * sizeof(T)``; the library exports the same number as
+    ``stsp_swe_tracer_lds_tl`` and ``HipCompute`` checks the two agree): the
+    window has 2 ghost layers, 3 with PPM tracers."""
+    ng = 3 if tracer_limiter == 4 else 2
+    ne = (bx + 1) * by + bx * (by + 1)
+    wf = (by + 2 * ng) * (bx + 2 * ng + 1)
+    bm = max(bx, by)
+    return ((5 + nq) * wf + 5 * ne + (4 + nq) * 4 * bm + 5 * 4 * bm + 3 * (bx + by + 2) + ne) * esize
+
+
+def choose_tracer_block(n: int, tiles: int = 0, cus: int = 0, nq: int = 1, esize: int = 8,
+                        tracer_limiter: int = 0):
     """Block shape of the tracer stage kernel, among ``TRACER_SHAPES`` by the
     rule of ``choose_block``: 16 x 16 while its grid fits the compute units in
     one pass and the 16 x 8 grid does not, else 16 x 8 (several blocks per CU:
-    five waves and half the LDS per block)."""
+    five waves and half the LDS per block).  16 x 16 is not chosen where its
+    launch would not fit in ``TRACER_LDS_MAX`` (fp64, four PPM tracers:
+    70 016 bytes)."""
     def count(bx, by):
         return tiles * -(-n // bx) * -(-n // by)
-    if tiles and cus and count(16, 16) <= cus < count(16, 8):
+    if tiles and cus and count(16, 16) <= cus < count(16, 8) and \
+            tracer_lds_bytes(16, 16, nq, esize, tracer_limiter) <= TRACER_LDS_MAX:
         return (16, 16)
     return (16, 8)
 
@@ -192,7 +211,9 @@ class HipCompute:
         if e.block is None:
             cus = torch.cuda.get_device_properties(e.device).multi_processor_count
             if self.phys_id == 3:
-                bx, by = choose_tracer_block(n, T, cus)
+                kp = phys.kernel_params()
+                bx, by = choose_tracer_block(n, T, cus, int(kp["nq"]), torch.tensor([], dtype=e.dtype).element_size(),
+                                             int(kp.get("tracer_limiter", 0)))
             else:
                 bx, by = choose_block(n, T, cus, getattr(phys, "limiter", 0), torch.tensor([], dtype=e.dtype).element_size())
             # streaming stage once the rank streams: measured C720 (3.1M cells, 12k per CU)
@@ -239,8 +260,8 @@ class HipCompute:
             assert int(t["pe_base"].min()) >= -3 and int(t["pe_base"].max()) <= n + 1
             # the kernel reads the interpolation pair (b, b + 1) of ghost layer k < KG
             # from the block's window: -NG <= b - j <= NG - 1 for strip cell j
-            # (PLR: NG = 2, one layer; PPM: NG = 3, two layers)
-            ppm = int(phys.kernel_params().get("limiter", 0)) == 4
+            # (PLR: NG = 2, one layer; PPM, also for the tracers alone: NG = 3, two layers)
+            ppm = 4 in (int(phys.kernel_params().get("limiter", 0)), int(phys.kernel_params().get("tracer_limiter", 0)))
             ng_k, kg = (3, 2) if ppm else (2, 1)
             off = t["pe_base"][:, :, :kg].long() - torch.arange(n, device=t["pe_base"].device)
             assert int(off.min()) >= -ng_k and int(off.max()) <= ng_k - 1, \
@@ -248,17 +269,24 @@ class HipCompute:
         if self.phys_id in SWE_KERNELS:
             assert t["mx"].shape == (T, 3, n + 1) and t["my"].shape == (T, 3, n + 1)
             assert t["cgeo"].shape == (T, n, n, 8)
-        self._nq = 0
+        self._nq = self._tlim = 0
         if self.phys_id == 3:      # (h, M, hq_k): the kernel strides the state and the receive buffer by 4 + nq
             self._nq = int(phys.kernel_params()["nq"])
             lim3 = int(phys.kernel_params().get("limiter", 0))
             assert 1 <= self._nq <= 4 and F == 4 + self._nq, "tracer state: 4 SWE fields + 1 to 4 tracers"
             assert 0 <= lim3 <= 3, "the tracer stage kernel has the PLR limiters 0 to 3"
-            assert plan.ng >= 2 and "pedge" in t and "pe_base" in t
-            self.lib.stsp_swe_tracer_lds.argtypes = [ctypes.c_int] * 4
-            self.lib.stsp_swe_tracer_lds.restype = ctypes.c_int
-            lds = int(self.lib.stsp_swe_tracer_lds(self.dcode, bx, by, self._nq))
-            assert 0 < lds <= 65536, f"tracer stage kernel: {lds} bytes of LDS per block"
+            self._tlim = int(phys.kernel_params().get("tracer_limiter", 0))
+            assert self._tlim in (0, 4), "tracer reconstruction: 0 (as the limiter) or 4 (monotone PPM)"
+            assert plan.ng >= (3 if self._tlim == 4 else 2) and "pedge" in t and "pe_base" in t
+            self.lib.stsp_swe_tracer_lds_tl.argtypes = [ctypes.c_int] * 5
+            self.lib.stsp_swe_tracer_lds_tl.restype = ctypes.c_int
+            lds = int(self.lib.stsp_swe_tracer_lds_tl(self.dcode, bx, by, self._nq, self._tlim))
+            esize = torch.tensor([], dtype=e.dtype).element_size()
+            assert lds == tracer_lds_bytes(bx, by, self._nq, esize, self._tlim), "tracer stage kernel: LDS size rule"
+            if lds > TRACER_LDS_MAX:
+                raise ValueError(f"tracer stage kernel: block {(bx, by)} with {self._nq} tracers"
+                                 f"{' on PPM' if self._tlim == 4 else ''} needs {lds} bytes of LDS per block, "
+                                 f"more than the {TRACER_LDS_MAX} a launch gets; use block (16, 8)")
         assert S == T * (n + 2 * plan.ng) ** 2
         pm = plan.push_map
         assert pm.shape == (T, 4, plan.ng, n) and pm.max(initial=-1) < S
@@ -353,6 +381,7 @@ class HipCompute:
         if self.phys_id in SWE_KERNELS:
             d.mx, d.my, d.cgeo = p(t["mx"]), p(t["my"]), p(t["cgeo"])
         d.nq = self._nq
+        d.tracer_limiter = self._tlim
         if "pedge" in t:
             d.pedge = p(t["pedge"])
         if "pe_base" in t:

@@ -45,7 +45,7 @@ class StageDesc(ctypes.Structure):
         # carried tile-corner ghosts (parallel/layout.py::corner_sources)
         ("cgmap", ctypes.c_void_p), ("cpush", ctypes.c_void_p),
         # shallow water with tracers (swe_tracer_stage.hip)
-        ("nq", ctypes.c_int),
+        ("nq", ctypes.c_int), ("tracer_limiter", ctypes.c_int),
     ]
 
 

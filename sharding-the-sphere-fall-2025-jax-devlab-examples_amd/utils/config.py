@@ -61,6 +61,9 @@ class PhysicsConfig:
     # the flow (models/initial_conditions.py::tracer_field: constant | cosine_bell |
     # cap | gradient); null or empty = none
     tracers: Optional[List[str]] = None
+    # with tracers: null = the mixing ratios use `limiter`; ppm = the mixing ratios
+    # alone on the monotone PPM (halo 3) while (h, v) keep `limiter`
+    tracer_limiter: Optional[str] = None
     # shallow water only: scale-selective dissipation applied between model steps
     # (models/dissipation.py): {order: 1 | 2, nu: m^2/s (order 1) or m^4/s (order 2),
     # interval: steps between applications (default 1), depth: diffuse the free
