@@ -43,12 +43,52 @@ class SolverDiagnostics:
         self._restored_particles = None
 
     # ---- names, sources, rank combine -------------------------------------------------
+    def layers(self) -> int:
+        """Layers of a layered shallow-water run (``physics.layers``), else 0."""
+        return int(self.physics.nl) if getattr(self.physics, "kernel_id", None) == 4 else 0
+
+    def layer_names(self) -> List[str]:
+        """The computed names of a layered run: the interface heights ``eta0``
+        (= b + h_0 + h_1 + .., the free surface), ``eta1`` (= b + h_1 + ..), ..
+        and per layer ``vorticity0``, ``divergence0``, ``pv0``, ``vorticity1``, .."""
+        L = self.layers()
+        return [f"eta{k}" for k in range(L)] + [f"{d}{k}" for k in range(L) for d in DERIVED_FIELDS]
+
+    def _layer_tiles_all(self) -> List[torch.Tensor]:
+        """[len(layer_names()), T, n, n] of every engine of this process.  The
+        derived fields of layer k go through the existing derived path on the
+        layer's rows (``DerivedFields.set_layer``): all engines start, then all
+        finish, layer by layer."""
+        L = self.layers()
+        ds = [e.derived_fields for e in self.engines]
+        per = []
+        for k in range(L):
+            per.append([f.clone() for f, _ in self._derived_all(layer=k)])
+        for d in ds:
+            d.set_layer(0)
+        out = []
+        for j, e in enumerate(self.engines):
+            qi = e.tiles_view().detach()
+            eta, acc = [], e.tens["b"]
+            for k in reversed(range(L)):
+                acc = acc + qi[4 * k]
+                eta.insert(0, acc)
+            out.append(torch.stack(eta + [per[k][j][i] for k in range(L) for i in range(len(DERIVED_FIELDS))]))
+        return out
+
     def mix_names(self) -> List[str]:
-        """``q0 ..``: the mixing ratios hq_k / h of a shallow-water run with tracers."""
+        """The names computed from the state besides the prognostic ones: ``q0
+        ..``, the mixing ratios hq_k / h of a shallow-water run with tracers;
+        ``layer_names()`` of a layered run."""
+        if self.layers():
+            return self.layer_names()
         return [f"q{k}" for k in range(getattr(self.physics, "nq", 0))]
 
     def _mixing_tiles(self, e) -> torch.Tensor:
-        """[NQ, T, n, n] mixing ratios of engine ``e`` (0 where h = 0)."""
+        """[NQ, T, n, n] mixing ratios of engine ``e`` (0 where h = 0); of a
+        layered run its ``layer_names()`` fields."""
+        if self.layers():
+            return self._layer_tiles_all()[[id(x) for x in self.engines].index(id(e))]
         qi = e.tiles_view().detach()
         return torch.stack([self.physics.mixing_ratio(qi, k) for k in range(self.physics.nq)])
 
@@ -91,6 +131,10 @@ class SolverDiagnostics:
                 raise ValueError(f"{name!r} is a vector component, not a scalar on the sphere: it has no "
                                  f"spherical-harmonic spectrum; use ke_spectrum for the winds")
             if name in DERIVED_FIELDS or name in LATLON_WINDS:
+                if self.layers():
+                    raise ValueError(f"{name!r} on a layered run: derived fields are per layer "
+                                     f"({name if name in DERIVED_FIELDS else 'vorticity'}0, ..); choose from "
+                                     f"{self.fields + self.layer_names()}")
                 if self.physics.name != "swe":
                     kind = "derived fields" if name in DERIVED_FIELDS else "winds"
                     raise ValueError(f"{kind} are defined for the shallow-water model, not {self.physics.name!r}")
@@ -166,13 +210,19 @@ class SolverDiagnostics:
         return acc
 
     # ---- derived fields (models/derived.py, ops/derived.py) -------------------------
-    def _derived_all(self):
+    def _derived_all(self, layer: Optional[int] = None):
         """[(fields [3, T, n, n], inv [8])] of every engine of this process.
         Ranks with remote ghosts exchange first: all engines start, then all
-        finish (the virtual cluster's lockstep)."""
+        finish (the virtual cluster's lockstep).  ``layer``: of that layer of a
+        layered run (buffers overwritten by the next call)."""
         if self.physics.name != "swe":
             raise ValueError(f"derived fields are defined for the shallow-water model, not {self.physics.name!r}")
+        if self.layers() and layer is None:
+            raise ValueError(f"derived fields of a layered run are per layer: use {self.layer_names()}")
         ds = [e.derived_fields for e in self.engines]
+        if layer is not None:
+            for d in ds:
+                d.set_layer(layer)
         for d in ds:
             d.start()
         for d in ds:
@@ -182,6 +232,13 @@ class SolverDiagnostics:
     def derived_field(self, name: str) -> Optional[np.ndarray]:
         """[6, N, N] of ``vorticity``, ``divergence`` or ``pv`` on rank 0 (None
         elsewhere), like ``global_field``."""
+        if self.layers():
+            names = self.layer_names()
+            if name not in names:
+                raise ValueError(f"unknown derived field {name!r} of a layered run; choose from {names}")
+            tiles = self._layer_tiles_all()
+            return self._gather_tiles({e.rank: x[names.index(name)].detach().cpu().double().numpy()
+                                       for e, x in zip(self.engines, tiles)})
         if name not in DERIVED_FIELDS:
             raise ValueError(f"unknown derived field {name!r}; choose from {list(DERIVED_FIELDS)}")
         k = DERIVED_FIELDS.index(name)
@@ -226,7 +283,7 @@ class SolverDiagnostics:
     # ---- lat-lon output (models/latlon.py, ops/latlon.py) ---------------------------
     def latlon_names(self) -> List[str]:
         """What ``latlon_field`` / ``zonal_mean`` accept for this model."""
-        swe = self.physics.name == "swe"
+        swe = self.physics.name == "swe" and not self.layers()
         return list(self.fields) + self.mix_names() + (list(DERIVED_FIELDS) + list(LATLON_WINDS) if swe else [])
 
     def _latlon_arrays(self, names, nlat: int, nlon: int, der=None):
@@ -321,6 +378,9 @@ class SolverDiagnostics:
         same particles from the summed velocity terms."""
         if self.physics.name != "swe":
             raise ValueError(f"particles are carried by the shallow-water model, not {self.physics.name!r}")
+        if self.layers():
+            raise ValueError("particles on a layered run are not supported: they follow the winds of one "
+                             "shallow-water layer")
         self._particles = [e.particles(lat, lon, interval) for e in self.engines]
         self._pinterval = int(interval)
         self._particles_stage(1)
@@ -402,7 +462,8 @@ class SolverDiagnostics:
     # ---- spectra (models/spectra.py, ops/spectra.py) --------------------------------
     def spectrum_names(self) -> List[str]:
         """What ``sh_coefficients`` / ``spectrum`` accept for this model."""
-        return list(self.fields) + self.mix_names() + (list(DERIVED_FIELDS) if self.physics.name == "swe" else [])
+        swe = self.physics.name == "swe" and not self.layers()
+        return list(self.fields) + self.mix_names() + (list(DERIVED_FIELDS) if swe else [])
 
     def _spectra_coeffs(self, names, lmax: int, der=None):
         """Coefficients [len(names), 2, L+1, L+1] float64 of the current state
@@ -435,9 +496,9 @@ class SolverDiagnostics:
         return None if r is None else spectra_power(r)[0].detach().cpu().numpy()
 
     def _ke_spectrum(self, lmax: int, der=None):
-        if self.physics.name != "swe":
-            raise ValueError(f"the kinetic-energy spectrum is defined for the shallow-water model, "
-                             f"not {self.physics.name!r}")
+        if self.physics.name != "swe" or self.layers():
+            raise ValueError(f"the kinetic-energy spectrum is defined for the one-layer shallow-water model, "
+                             f"not {'a layered run' if self.layers() else repr(self.physics.name)}")
         r = self._spectra_coeffs(["vorticity", "divergence"], lmax, der=der)
         return None if r is None else spectra_ke(r[0], r[1], self.grid.radius)
 
@@ -451,7 +512,7 @@ class SolverDiagnostics:
         """The ``io.spectra`` power per degree of a history frame, [len(names)
         (+ 1: the kinetic energy, shallow water), L+1] (rank 0; None elsewhere)."""
         L = self.cfg.io.spectra
-        swe = self.physics.name == "swe"
+        swe = self.physics.name == "swe" and not self.layers()
         if der is None and (swe or any(f in DERIVED_FIELDS for f in names)):
             der = self._derived_all()
         r = self._spectra_coeffs(names, L, der=der)
@@ -544,6 +605,9 @@ class SolverDiagnostics:
     def invariants(self) -> Dict[str, float]:
         """mass, energy, potential_enstrophy, circulation, abs_circulation
         (sums over the sphere) and max_courant (maximum) of the current state."""
+        if self.layers():
+            raise ValueError("invariants() is defined for one shallow-water layer; a layered run reports mass0, "
+                             "mass1, .. and energy through diagnostics()")
         sums: Dict[str, float] = {}
         cmax = 0.0
         for _, inv in self._derived_all():

@@ -38,7 +38,7 @@ from .models.derived import FIELDS as DERIVED_FIELDS, INVARIANTS
 from .models.diffusion import OPERATORS, ConsistentDiffusion, Diffusion
 from .models.geometry import DAY, EARTH_RADIUS, CubedSphereGrid
 from .models.spectra import check_lmax
-from .models.swe import MAX_TRACERS, ShallowWater, ShallowWaterTracers
+from .models.swe import MAX_TRACERS, LayeredShallowWater, ShallowWater, ShallowWaterTracers
 from .parallel.comm import NativeBuffers, TorchDistTransport
 from .parallel.layout import TileLayout
 from .parallel.mesh import setup_sharding
@@ -88,6 +88,12 @@ def make_physics(pc) -> Any:
         raise ValueError(f"physics.operator: one of {list(OPERATORS)} expected, not {op!r}")
     if op == "consistent" and model != "diffusion":
         raise ValueError(f"physics.operator: consistent is defined for the diffusion model, not {model!r}")
+    layers = layers_spec(pc)
+    if layers is not None:
+        if tracers:
+            raise ValueError("physics.layers with physics.tracers: tracers ride one shallow-water layer; a "
+                             "layered run carries none")
+        return LayeredShallowWater(case, limiter=lim, alpha=pc.alpha, **layers)
     if model == "swe":
         if tracers:
             return ShallowWaterTracers(case, tracers=list(tracers), limiter=lim, alpha=pc.alpha, tracer_limiter=tlim)
@@ -101,6 +107,35 @@ def make_physics(pc) -> Any:
             raise ValueError(f"physics.kappa: a number expected, not {pc.kappa!r}") from None
         return (ConsistentDiffusion if op == "consistent" else Diffusion)(kappa=kappa, case=case)
     raise ValueError(f"unknown physics model {pc.model!r}")
+
+
+def layers_spec(pc) -> Optional[Dict[str, Any]]:
+    """``physics.layers`` checked: the keyword arguments {depths, density_ratio,
+    winds, jet_scale} of ``LayeredShallowWater``, or None when it is off."""
+    d = getattr(pc, "layers", None)
+    if d is None:
+        return None
+    if not isinstance(d, dict) or "depths" not in d:
+        raise ValueError(f"physics.layers: {{depths, density_ratio, winds, jet_scale}} expected, not {d!r}")
+    unknown = set(d) - {"depths", "density_ratio", "winds", "jet_scale"}
+    if unknown:
+        raise ValueError(f"physics.layers: unknown key(s) {sorted(unknown)}")
+    if pc.model.lower() != "swe":
+        raise ValueError(f"physics.layers: defined for the shallow-water model, not {pc.model!r}")
+    def numbers(key, v):
+        try:                                     # YAML 1.1 reads 4.0e3 (no sign in the exponent) as a string
+            return [float(x) for x in v]
+        except (TypeError, ValueError):
+            raise ValueError(f"physics.layers.{key}: a list of numbers expected, not {v!r}") from None
+    out: Dict[str, Any] = {"depths": numbers("depths", d["depths"])}
+    if len(out["depths"]) != 2:
+        raise ValueError(f"physics.layers.depths: two layers [H_0, H_1] expected, not {d['depths']!r}")
+    if d.get("winds") is not None:
+        out["winds"] = numbers("winds", d["winds"])
+    for key in ("density_ratio", "jet_scale"):
+        if d.get(key) is not None:
+            out[key] = numbers(key, [d[key]])[0]
+    return out
 
 
 def dissipation_spec(pc) -> Optional[Dict[str, Any]]:
@@ -130,6 +165,9 @@ def dissipation_spec(pc) -> Optional[Dict[str, Any]]:
         raise ValueError(f"physics.dissipation: depth must be true or false, not {depth!r}")
     if pc.model.lower() != "swe":
         raise ValueError(f"physics.dissipation: defined for the shallow-water model, not {pc.model!r}")
+    if getattr(pc, "layers", None) is not None:
+        raise ValueError("physics.dissipation with physics.layers: the dissipation operator acts on one "
+                         "shallow-water layer (h, M); a layered run takes none")
     if pc.tracers and depth:
         raise ValueError("physics.dissipation with physics.tracers: only depth: false is accepted (diffusing h "
                          "would change the mixing ratios hq / h)")
@@ -305,8 +343,8 @@ class Solver(SolverDiagnostics):
         N, t = c.grid.N, c.parallelization.tiles_per_edge
         phys0 = make_physics(c.physics)
         if c.runtime.comm == "xgmi" and phys0.F not in (1, 4):
-            raise ValueError("runtime.comm = xgmi with physics.tracers: the direct xGMI exchange packs 1 or 4 "
-                             "fields; use comm: auto, ipc or rccl")
+            raise ValueError(f"runtime.comm = xgmi with physics.{'layers' if phys0.kernel_id == 4 else 'tracers'}: "
+                             f"the direct xGMI exchange packs 1 or 4 fields; use comm: auto, ipc or rccl")
         # PPM reads three ghost layers: widen the halo if the config asks for fewer
         self.layout = TileLayout(N, t, nd, ng=max(c.grid.halo, phys0.halo), owner=self.sharding.owner)
         self.grid = self._geometry_stage(N, c.grid.radius or EARTH_RADIUS)
@@ -347,6 +385,9 @@ class Solver(SolverDiagnostics):
             if unknown:
                 raise ValueError(f"io.history_fields: unknown field(s) {unknown}; choose from "
                                  f"{self.fields + self.mix_names() + list(DERIVED_FIELDS)}")
+            if self.layers() and any(f in DERIVED_FIELDS for f in hf):
+                raise ValueError(f"io.history_fields: derived fields of a layered run are per layer; choose from "
+                                 f"{self.fields + self.mix_names()}")
             if phys0.name != "swe" and any(f in DERIVED_FIELDS for f in hf):
                 raise ValueError(f"io.history_fields: derived fields {list(DERIVED_FIELDS)} need the "
                                  f"shallow-water model, not {phys0.name!r}")
@@ -468,6 +509,15 @@ class Solver(SolverDiagnostics):
         None where the case has no closed form (and on other ranks)."""
         from .models.errors import williamson_norms
         exact = getattr(self.physics, "exact", None)
+        if self.layers() > 1:      # per layer: h0_l1, h0_l2, h0_linf, h1_l1, ..
+            g = self.gather_global()
+            ht = exact(self.grid, self.time)
+            if g is None or ht is None:
+                return None
+            out = {}
+            for k in range(self.layers()):
+                out.update({f"h{k}_{n}": v for n, v in williamson_norms(g[4 * k], ht[k], self.grid.areas()).items()})
+            return out
         h = self.global_field(0)
         if exact is None or h is None:
             return None
@@ -774,12 +824,12 @@ class Solver(SolverDiagnostics):
                 # the same frames on the lat-lon grid: the selected fields, or the
                 # prognostic ones plus the winds of the shallow-water model
                 lfields = list(hfields) if io.history_fields is not None else (
-                    self.fields + (list(LATLON_WINDS) if self.physics.name == "swe" else []))
+                    self.fields + (list(LATLON_WINDS) if self.physics.name == "swe" and not self.layers() else []))
                 hll = LatLonHistoryWriter(os.path.join(out, "history_latlon.zarr"), lfields, io.latlon[0],
                                           io.latlon[1], n_out, attrs=wattrs) if self.rank == 0 else None
                 frames.append((lambda der: self._latlon_frame(lfields, der), hll, as_f64))
             if io.spectra is not None:
-                snames = list(hfields) + (["ke"] if self.physics.name == "swe" else [])
+                snames = list(hfields) + (["ke"] if self.physics.name == "swe" and not self.layers() else [])
                 hsp = SpectraHistoryWriter(os.path.join(out, "history_spectra.zarr"), snames, io.spectra, n_out,
                                            attrs=wattrs) if self.rank == 0 else None
                 frames.append((lambda der: self._spectra_frame(list(hfields), der), hsp, as_f64))
@@ -986,7 +1036,7 @@ class Solver(SolverDiagnostics):
         rec = dict(step=self.step_count, time_s=self.time, sim_days=self.time / DAY, dt=self.dt)
         wall = time.perf_counter() - wall0
         rec["cell_updates_per_s"] = cells * done / max(wall, 1e-12)
-        swe = self.physics.name == "swe"
+        swe = self.physics.name == "swe" and not self.layers()      # a layered run: mass0, mass1, energy only
         nq = getattr(self.physics, "nq", 0)
         if not deferred:
             extra = {}
@@ -1036,7 +1086,7 @@ class Solver(SolverDiagnostics):
         vals = [v.reshape(()).to(torch.float64) for e in self.engines
                 for v in e.physics.diagnostics(e.tiles_view(), e.tens).values()]
         stage([flag, torch.stack(vals)], True)
-        if derived and self.physics.name == "swe":      # the derived-field kernels of the metrics records
+        if derived and self.physics.name == "swe" and not self.layers():      # the derived-field kernels of the metrics records
             self._derived_all()
         torch.cuda.current_stream().synchronize()
 

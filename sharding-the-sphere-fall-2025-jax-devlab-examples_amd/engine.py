@@ -232,13 +232,16 @@ class Engine:
             self._derived = DerivedFields(self)
         return self._derived
 
-    def derived(self, exchange: bool = True):
+    def derived(self, exchange: bool = True, layer: Optional[int] = None):
         """(fields [3, T, n, n] = vorticity, divergence, potential vorticity;
         inv [8] float64, ``models.derived.INVARIANTS`` order) of the current
         state, as device tensors.  A rank with remote ghosts exchanges first;
         ``exchange=False`` when the caller ran ``derived_fields.start()`` /
-        ``finish()`` itself (several engines in one process)."""
+        ``finish()`` itself (several engines in one process).  ``layer``: of
+        that layer of a layered shallow-water state (``set_layer``)."""
         d = self.derived_fields
+        if layer is not None:
+            d.set_layer(layer)
         if exchange:
             d.start()
             d.finish()

@@ -16,6 +16,8 @@ invariant representation the reference exchanges across cube edges (PDF s.18
                         the perturbation.
 * ``tracer_field``      mixing ratios in [0, 1] for the shallow-water tracers:
                         ``constant``, ``cosine_bell``, ``cap``, ``gradient``.
+* ``layered_fields``    two-layer (stacked shallow water) states: ``tc2``, ``rest``,
+                        ``tc5``, ``layered_jet``, ``layered_jet_balanced``.
 * ``lima_flag``         checkerboard heat source on the top panel (face 0) on a
                         1 K background (PDF s.12 / s.17, log scale 1..1000 K).
 """
@@ -139,8 +141,8 @@ def galewsky_wind(lat):
     return np.where(inside, GALEWSKY_UMAX / en * np.exp(1.0 / x), 0.0)
 
 
-def _galewsky_integrand(lat, radius, omega):
-    u = galewsky_wind(lat)
+def _galewsky_integrand(lat, radius, omega, scale=1.0):
+    u = galewsky_wind(lat) if scale == 1.0 else scale * galewsky_wind(lat)
     return radius * u * (2.0 * omega * np.sin(lat) + u * np.tan(lat) / radius)
 
 
@@ -152,15 +154,15 @@ def _gauss_on(a, b, fn, nodes):
     return half * (fn(mid[..., None] + half[..., None] * x) * w).sum(-1)
 
 
-def galewsky_depth(lat, radius=EARTH_RADIUS, omega=OMEGA, g=GRAVITY, nodes=GALEWSKY_NODES):
-    """Balanced depth h(phi) of the jet (m):
+def galewsky_depth(lat, radius=EARTH_RADIUS, omega=OMEGA, g=GRAVITY, nodes=GALEWSKY_NODES, scale=1.0):
+    """Balanced depth h(phi) of the jet (m), of ``scale`` times its wind:
     g h(phi) = g h0 - int_{-pi/2}^{phi} a u (f + u tan(phi') / a) dphi'
     by composite Gauss-Legendre quadrature on the host (``GALEWSKY_PANELS``
     fixed panels across the jet with ``nodes`` nodes each, and a last partial
     panel up to phi); h0 makes the analytic global mean depth 10 000 m."""
     lat = np.asarray(lat, dtype=np.float64)
     p0, p1, K = GALEWSKY_PHI0, GALEWSKY_PHI1, GALEWSKY_PANELS
-    fn = lambda x: _galewsky_integrand(x, radius, omega)
+    fn = lambda x: _galewsky_integrand(x, radius, omega, scale)
     edges = np.linspace(p0, p1, K + 1)
     cum = np.concatenate([[0.0], np.cumsum(_gauss_on(edges[:-1], edges[1:], fn, nodes))])
     x = np.clip(lat, p0, p1)
@@ -253,3 +255,87 @@ def tracer_field(name, p, radius=EARTH_RADIUS):
     if name == "gradient":
         return 0.5 * (1.0 + p[..., 2])
     raise ValueError(f"unknown tracer initial condition {name!r}; choose from {list(TRACER_FIELDS)}")
+
+
+# ---- two-layer shallow water (models/swe.py::LayeredShallowWater) -----------------
+LAYER_CASES = ("tc2", "rest", "tc5", "layered_jet", "layered_jet_balanced")
+LAYER_DEPTHS = {"tc2": (4000.0, 4000.0), "rest": (1000.0, 1000.0), "tc5": (2000.0, 5960.0),
+                "layered_jet": (5000.0, 5000.0), "layered_jet_balanced": (5000.0, 5000.0)}
+LAYER_WINDS = (0.5, 0.4)       # tc2: layer winds as fractions of TC2's u0
+LAYER_JET_SCALE = 0.25         # layered_jet: the Galewsky wind times this, in the top layer
+
+
+def layered_fields(case, p, depths=None, density_ratio=0.9, winds=None, jet_scale=None, alpha=0.0,
+                   radius=EARTH_RADIUS, omega=OMEGA, g=GRAVITY):
+    """Two layers (0 on top, r = rho_0 / rho_1 = ``density_ratio`` < 1) with
+    resting depths ``depths`` = [H_0, H_1].  Returns (h [2, ...], wind
+    [2, ..., 3], b).  The top layer's pressure is g (b + h_0 + h_1), the bottom
+    layer's g (b + r h_0 + h_1):
+
+    * ``tc2``   exact steady state: layer k in solid-body rotation
+      U_k = winds[k] u0 (TC2's u0 and ``alpha``).  With A_k = R Omega U_k +
+      U_k^2 / 2 and TC2's s:  h_0 + h_1 = H_0 + H_1 - A_0 s^2 / g  and
+      r h_0 + h_1 = r H_0 + H_1 - A_1 s^2 / g,  so
+      h_0 = H_0 - (A_0 - A_1) s^2 / (g (1 - r));
+    * ``rest``  uniform layers, no wind;
+    * ``tc5``   both layers at TC5's u0 over its mountain: h_0 = H_0 and
+      h_1 = H_1 - (R Omega u0 + u0^2 / 2) sin^2(lat) / g - b;
+    * ``layered_jet`` / ``layered_jet_balanced``  ``jet_scale`` times the
+      Galewsky wind in the top layer, the bottom layer at rest: the free surface
+      is H_0 + H_1 + d with d the balanced Galewsky depth of the scaled wind
+      minus its mean, the interface makes r h_0 + h_1 constant; ``layered_jet``
+      adds the Galewsky bump to h_0.
+
+    Parameters that make a thickness non-positive are refused."""
+    if case not in LAYER_CASES:
+        raise ValueError(f"unknown layered shallow-water case {case!r}; choose from {list(LAYER_CASES)}")
+    depths = LAYER_DEPTHS[case] if depths is None else depths
+    if len(depths) != 2 or not all(float(H) > 0 for H in depths):
+        raise ValueError(f"layered shallow water: depths = [H_0, H_1], both positive, expected, not {list(depths)!r}")
+    H0, H1 = float(depths[0]), float(depths[1])
+    r = float(density_ratio)
+    if not 0.0 < r < 1.0:
+        raise ValueError(f"layered shallow water: density_ratio = rho_0 / rho_1 in (0, 1) expected, not {r!r}")
+    lon, lat = xyz_to_lonlat(p)
+    zero = np.zeros(p.shape[:-1])
+    if case == "rest":
+        h = np.stack([zero + H0, zero + H1])
+        wind = np.zeros((2,) + p.shape)
+        b = zero
+    elif case == "tc2":
+        winds = LAYER_WINDS if winds is None else winds
+        if len(winds) != 2:
+            raise ValueError(f"layered shallow water: winds = [w_0, w_1] expected, not {list(winds)!r}")
+        u0 = 2.0 * math.pi * radius / (12.0 * DAY)
+        U = [float(w) * u0 for w in winds]
+        A = [radius * omega * u + 0.5 * u * u for u in U]
+        s = -np.cos(lon) * np.cos(lat) * math.sin(alpha) + np.sin(lat) * math.cos(alpha)
+        h0 = H0 - (A[0] - A[1]) * s * s / (g * (1.0 - r))
+        h1 = H0 + H1 - A[0] * s * s / g - h0
+        h = np.stack([h0, h1])
+        wind = np.stack([solid_body_wind(p, u, alpha, radius) for u in U])
+        b = zero
+    elif case == "tc5":
+        u0 = 20.0
+        b = tc5_mountain(p)
+        h1 = H1 - (radius * omega * u0 + 0.5 * u0 * u0) * np.sin(lat) ** 2 / g - b
+        h = np.stack([zero + H0, h1])
+        w = solid_body_wind(p, u0, 0.0, radius)
+        wind = np.stack([w, w])
+    else:
+        sc = LAYER_JET_SCALE if jet_scale is None else float(jet_scale)
+        d = galewsky_depth(lat, radius, omega, g, scale=sc) - GALEWSKY_MEAN_DEPTH
+        h0 = H0 + d / (1.0 - r)
+        h1 = H1 - r * d / (1.0 - r)
+        if case == "layered_jet":
+            h0 = h0 + galewsky_perturbation(lon, lat)
+        h = np.stack([h0, h1])
+        e, _ = lonlat_vectors(p)
+        wind = np.stack([(sc * galewsky_wind(lat))[..., None] * e, np.zeros(p.shape)])
+        b = zero
+    for k in range(2):
+        if not h[k].min() > 0:
+            raise ValueError(f"layered shallow water, case {case!r}: the thickness of layer {k} is not positive "
+                             f"(minimum {h[k].min():.6g} m) with depths {[H0, H1]}, density_ratio {r}; "
+                             f"use deeper layers, weaker winds or a smaller density_ratio")
+    return h, wind, b

@@ -293,3 +293,244 @@ class ShallowWaterTracers(ShallowWater):
         for k in range(self.nq):
             d[f"tracer_mass_{k}"] = (qi[4 + k] * A).sum()
         return d
+
+
+class LayeredShallowWater(ShallowWater):
+    """Stacked (isopycnal) shallow water: L layers of constant density, layer 0
+    on top, rho_0 < ... < rho_{L-1}.
+
+    State (h_0, M_0, h_1, M_1, ...), field-major, M_k = h_k v_k Cartesian.  Layer
+    k is the parent's layer (PLR on (h_k, v_k), panel-edge treatment, Rusanov
+    flux, curvature balance, Coriolis, static -g h_k grad b, tangent projection,
+    the h = 0 guard of the primitive division) over a topography that moves, the
+    other layers:
+
+    * the momentum source gains  -g h_k grad(c_k)  with
+      c_k = sum_{j<k} (rho_j / rho_k) h_j + sum_{j>k} h_j  (layers above press
+      with their density ratio, layers below lift with weight 1), so that
+      b + c_k + h_k is the layer's Montgomery height.  grad(c_k) is the Gauss
+      sum over the four faces of (cbar_face - c_cell) m L / A with the face's
+      sign, projected onto the tangent plane at the cell centre; cbar_face is
+      the mean (hL + hR) / 2 of the contributing layers' reconstructed edge
+      states, the states the flux uses (single-valued across a cube edge).
+      c_cell is subtracted before anything is multiplied: uniform layers give
+      exactly zero;
+    * the Rusanov speed of every layer is |v_k . m| + sqrt(g H), H = sum_j h_j
+      of the cell averages, the larger of the two adjacent cells: sqrt(g H)
+      bounds the external and all internal wave speeds while the densities
+      increase downwards.
+
+    With one layer every operation is the parent's in the parent's order:
+    bit-identical to ``ShallowWater``.  PLR limiters only.
+
+    ``depths``: resting depths [H_0, ..]; None = one layer with the case's own
+    depth (the parent's cases).  Two layers take the cases of
+    ``initial_conditions.layered_fields``; more than two only ``rest``.
+    ``density_ratio`` r = rho_k / rho_{k+1} of adjacent layers.
+
+    Diagnostics: mass_k = sum(h_k A) and one energy
+    sum_k (rho_k / rho_{L-1}) [ |M_k|^2 / (2 h_k) + g h_k (b + sum_{j>k} h_j + h_k / 2) ] A,
+    whose derivative by h_k is (rho_k / rho_{L-1}) g times the Montgomery height
+    b + c_k + h_k above."""
+    kernel_id = 4
+
+    def __init__(self, case: str = "tc2", depths=None, density_ratio: float = 0.9, winds=None, jet_scale=None, **kw):
+        super().__init__(case, **kw)
+        if self.limiter == PPM:
+            raise ValueError("layered shallow water: PPM (limiter 4) is not supported, the layer stage kernel "
+                             "reconstructs with the PLR limiters 0 to 3 only")
+        self.depths = None if depths is None else [float(H) for H in depths]
+        self.nl = 1 if self.depths is None else len(self.depths)
+        if self.nl < 1:
+            raise ValueError("layered shallow water: depths needs at least one layer")
+        self.density_ratio = float(density_ratio)
+        if self.nl > 1 and not 0.0 < self.density_ratio < 1.0:
+            raise ValueError(f"layered shallow water: density_ratio = rho_0 / rho_1 in (0, 1) expected, "
+                             f"not {density_ratio!r}")
+        self.winds = None if winds is None else [float(w) for w in winds]
+        self.jet_scale = None if jet_scale is None else float(jet_scale)
+        if self.nl == 2 and case not in ic.LAYER_CASES:
+            raise ValueError(f"unknown layered shallow-water case {case!r}; choose from {list(ic.LAYER_CASES)}")
+        if self.nl > 2 and case != "rest":
+            raise ValueError(f"layered shallow water with {self.nl} layers has the case 'rest' only, not {case!r}")
+        L = self.nl
+        self.rho = [self.density_ratio ** (L - 1 - k) for k in range(L)]     # relative to the bottom layer
+        # coupling weights: c_k = sum_j cw[k][j] h_j
+        self.cw = [[(self.rho[j] / self.rho[k] if j < k else 1.0) if j != k else 0.0 for j in range(L)]
+                   for k in range(L)]
+        self.fields = [f"{name}{k}" for k in range(L) for name in ("h", "mx", "my", "mz")]
+
+    # ---- initial conditions --------------------------------------------
+    def global_fields(self, grid: CubedSphereGrid):
+        """(h, wind, b): the parent's arrays with one layer, else h [L, 6, N, N]
+        and wind [L, 6, N, N, 3]."""
+        if self.nl == 1:
+            return super().global_fields(grid)
+        p = grid.centers()
+        if self.nl == 2:
+            return ic.layered_fields(self.case, p, self.depths, self.density_ratio, self.winds, self.jet_scale,
+                                     alpha=self.alpha, radius=grid.radius, omega=self.omega, g=self.g)
+        zero = np.zeros(p.shape[:-1])
+        return np.stack([zero + H for H in self.depths]), np.zeros((self.nl,) + p.shape), zero
+
+    def layer_fields(self, grid: CubedSphereGrid):
+        """(h [L, 6, N, N], wind [L, 6, N, N, 3], b) for any L."""
+        h, wind, b = self.global_fields(grid)
+        return (h[None], wind[None], b) if self.nl == 1 else (h, wind, b)
+
+    def exact(self, grid: CubedSphereGrid, t: float):
+        """True depths where the case is steady (tc2, rest): [6, N, N] with one
+        layer, else [L, 6, N, N]; else None."""
+        if self.case in ("tc2", "rest"):
+            return self.global_fields(grid)[0]
+        return None
+
+    def initial_state(self, geo: RankGeometry) -> np.ndarray:
+        if self.nl == 1:
+            return super().initial_state(geo)
+        h, wind, b = self.global_fields(geo.grid)
+        hl = [geo.gather_global(h[k]) for k in range(self.nl)]
+        q = np.empty((4 * self.nl,) + hl[0].shape)
+        for k in range(self.nl):
+            q[4 * k] = hl[k]
+            q[4 * k + 1:4 * k + 4] = np.moveaxis(hl[k][..., None] * geo.gather_global(wind[k]), -1, 0)
+        return q
+
+    def kernel_params(self):
+        return dict(super().kernel_params(), layers=self.nl, layer_r=self.density_ratio)
+
+    # ---- reference RHS ------------------------------------------------------
+    def _layer_flux(self, wL, wR, cL, cR, aL, aR, m, L):
+        """The parent's ``_flux`` with the sound speeds aL, aR = sqrt(g H) of the
+        two cells passed in."""
+        g = self.g
+        hL, hR = wL[0], wR[0]
+        vL, vR = wL[1:], wR[1:]
+        vnL = (vL * m).sum(0)
+        vnR = (vR * m).sum(0)
+        sL = ((cL[1:] * m).sum(0)).abs() + aL
+        sR = ((cR[1:] * m).sum(0)).abs() + aR
+        c = torch.maximum(sL, sR)
+        Fh = 0.5 * (hL * vnL + hR * vnR) - 0.5 * c * (hR - hL)
+        Fm = 0.5 * (hL * vL * vnL + hR * vR * vnR + 0.5 * g * (hL * hL + hR * hR) * m) - 0.5 * c * (hR * vR - hL * vL)
+        return torch.cat([Fh[None], Fm], 0) * L
+
+    def coupling_gradient(self, k, hLx, hRx, hLy, hRy, qi, tens):
+        """Tangent gradient [3, T, n, n] of c_k = sum_j cw[k][j] h_j: ``hLx`` ..
+        the layers' reconstructed depths [L, ...] at the x- and y-edges."""
+        cw = self.cw[k]
+        cbx = cby = cc = None
+        for j in range(self.nl):
+            if cw[j] == 0.0:
+                continue
+            tx, ty, tc = cw[j] * (0.5 * (hLx[j] + hRx[j])), cw[j] * (0.5 * (hLy[j] + hRy[j])), cw[j] * qi[4 * j]
+            cbx, cby, cc = (tx, ty, tc) if cbx is None else (cbx + tx, cby + ty, cc + tc)
+        if cbx is None:       # one layer: nothing presses or lifts
+            return torch.zeros_like(tens["ctr"])
+        mx = tens["mx"].permute(1, 0, 2)[:, :, None, :]
+        my = tens["my"].permute(1, 0, 2)[:, :, :, None]
+        ex, ey = tens["ex"], tens["ey"]
+        we, ww = (cbx[..., 1:] - cc) * ex[..., 1:], (cbx[..., :-1] - cc) * ex[..., :-1]
+        wn, ws = (cby[..., 1:, :] - cc) * ey[..., 1:, :], (cby[..., :-1, :] - cc) * ey[..., :-1, :]
+        gc = ((we * mx[..., 1:] - ww * mx[..., :-1]) + (wn * my[..., 1:, :] - ws * my[..., :-1, :])) * tens["invA"]
+        r = tens["ctr"]
+        return gc - (gc * r).sum(0) * r
+
+    def _primitives(self, qe):
+        """(h_k, v_k) of every layer [4 L, ...], v_k = 0 where h_k = 0."""
+        prim = []
+        for k in range(self.nl):
+            h = qe[4 * k]
+            safe = torch.where(h != 0, h, torch.ones_like(h))
+            prim.append(torch.stack([h, qe[4 * k + 1] / safe, qe[4 * k + 2] / safe, qe[4 * k + 3] / safe]))
+        return prim[0] if self.nl == 1 else torch.cat(prim)
+
+    def coupling_gradients(self, qe, qi, tens, n, g):
+        """[L, 3, T, n, n]: grad(c_k) of every layer of the window ``qe`` (the
+        arguments of ``rhs``)."""
+        (wL, wR, _, _), (yL, yR, _, _) = reconstruct(self._primitives(qe), tens, g, n, self.limiter)
+        return torch.stack([self.coupling_gradient(k, wL[0::4], wR[0::4], yL[0::4], yR[0::4], qi, tens)
+                            for k in range(self.nl)])
+
+    def rhs(self, qe, qi, tens, n, g):
+        L = self.nl
+        w = self._primitives(qe)
+        (wL, wR, cL, cR), (yL, yR, dL, dR) = reconstruct(w, tens, g, n, self.limiter)
+        mx = tens["mx"].permute(1, 0, 2)[:, :, None, :]
+        my = tens["my"].permute(1, 0, 2)[:, :, :, None]
+
+        def sound(c):      # sqrt(g H) of the cell averages
+            H = c[0]
+            for j in range(1, L):
+                H = H + c[4 * j]
+            return torch.sqrt(self.g * H)
+        axL, axR, ayL, ayR = sound(cL), sound(cR), sound(dL), sound(dR)
+        invA = tens["invA"]
+        r = tens["ctr"]
+        f = self.omega * 2.0 * r[2]
+        out = []
+        for k in range(L):
+            s = slice(4 * k, 4 * k + 4)
+            Fx = self._layer_flux(wL[s], wR[s], cL[s], cR[s], axL, axR, mx, tens["ex"])
+            Gy = self._layer_flux(yL[s], yR[s], dL[s], dR[s], ayL, ayR, my, tens["ey"])
+            dq = -((Fx[..., 1:] - Fx[..., :-1]) + (Gy[..., 1:, :] - Gy[..., :-1, :])) * invA
+            hc = qi[4 * k]
+            M = qi[4 * k + 1:4 * k + 4]
+            cor = torch.stack([r[1] * M[2] - r[2] * M[1], r[2] * M[0] - r[0] * M[2], r[0] * M[1] - r[1] * M[0]])
+            dq[1:] += -f * cor + (hc * hc) * tens["sbal"] - self.g * hc * tens["gradb"]
+            if L > 1:
+                dq[1:] -= self.g * hc * self.coupling_gradient(k, wL[0::4], wR[0::4], yL[0::4], yR[0::4], qi, tens)
+            out.append(dq)
+        return out[0] if L == 1 else torch.cat(out)
+
+    def finalize(self, out, tens):
+        r = tens["ctr"]
+        for k in range(self.nl):
+            M = out[4 * k + 1:4 * k + 4]
+            d = (M * r).sum(0)
+            out[4 * k + 1:4 * k + 4] = M - d * r
+        return out
+
+    def max_dt(self, grid: CubedSphereGrid, cfl: float = 0.9) -> float:
+        """The parent's bound with sqrt(g H) and the largest layer wind."""
+        if self.nl == 1:
+            return super().max_dt(grid, cfl)
+        h, wind, b = self.global_fields(grid)
+        speed = np.linalg.norm(wind, axis=-1).max(0) + np.sqrt(self.g * np.maximum(h.sum(0), 0))
+        return cfl * grid.min_spacing() / (2.0 * float(speed.max()))
+
+    def layer_state(self, q, k: int):
+        """(h_k, M_k) of a state [4 L, ...]: a contiguous slice (field-major)."""
+        if not 0 <= int(k) < self.nl:
+            raise ValueError(f"layer {k}: this physics carries {self.nl} layer(s)")
+        return q[4 * int(k):4 * int(k) + 4]
+
+    def derived(self, q, recv, gmap, cmap, tens, tabs, order, T, n, ng, dt, layer: int = 0):
+        """The parent's derived fields of layer ``layer``: its rows of the state
+        and the receive buffer (PV = (zeta + f) / h_k)."""
+        k = int(layer)
+        rv = recv[:, 4 * k:4 * k + 4] if recv is not None and recv.numel() else recv
+        return super().derived(self.layer_state(q, k), rv, gmap, cmap, tens, tabs, order, T, n, ng, dt)
+
+    def diagnostics(self, qi, tens):
+        if self.nl == 1:
+            d = super().diagnostics(qi, tens)
+            d["mass0"] = d["mass"]
+            return d
+        A = tens["area"]
+        b = tens["b"]
+        L = self.nl
+        d = {}
+        energy = None
+        for k in range(L):
+            h = qi[4 * k]
+            M = qi[4 * k + 1:4 * k + 4]
+            below = b
+            for j in range(k + 1, L):
+                below = below + qi[4 * j]
+            e = self.rho[k] * (0.5 * (M * M).sum(0) / h + self.g * h * (below + 0.5 * h))
+            energy = e if energy is None else energy + e
+            d[f"mass{k}"] = (h * A).sum()
+        d["mass"] = sum(d[f"mass{k}"] for k in range(L))
+        d["energy"] = (energy * A).sum()
+        return d

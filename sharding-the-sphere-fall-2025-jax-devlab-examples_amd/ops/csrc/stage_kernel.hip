@@ -934,9 +934,11 @@ extern "C" int stsp_march_launch(int dtype, int rows, const StageDesc* d, hipStr
 extern "C" int stsp_swe_tracer_launch(int dtype, int bx, int by, const StageDesc* d, hipStream_t stream);
 
 // bx == 64: the streaming shallow-water stage (march_kernel.hip), by = rows per wave;
-// phys == 3: shallow water with tracers (swe_tracer_stage.hip)
+// phys == 3: shallow water with tracers (swe_tracer_stage.hip);
+// phys == 4: two-layer shallow water (swe_layer_stage.hip)
 extern "C" int stsp_stage_launch(int phys, int dtype, int bx, int by, const StageDesc* d, hipStream_t stream) {
   if (phys == 3) return stsp_swe_tracer_launch(dtype, bx, by, d, stream);
+  if (phys == 4) return stsp_swe_layer_launch(dtype, bx, by, d, stream);
   if (bx == 64) return phys == 2 ? stsp_march_launch(dtype, by, d, stream) : -2;
   if (dtype == 1) return launch_d<double>(phys, bx, by, d, stream);
   if (dtype == 0) return launch_d<float>(phys, bx, by, d, stream);

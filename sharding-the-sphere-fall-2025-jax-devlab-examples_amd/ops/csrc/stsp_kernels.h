@@ -74,9 +74,15 @@ typedef struct StageDesc {
                         // the state then holds F = 4 + nq fields (h, M, hq_k) and recv is [R][4 + nq]
   int tracer_limiter;   // phys 3: reconstruction of the mixing ratios, 0 = as `limiter`, 4 = monotone PPM
                         // (interface values confined between their cells; needs mg >= 3)
+  double layer_r;       // two-layer shallow water (phys 4, swe_layer_stage.hip): density ratio rho_0 / rho_1
+                        // in (0, 1]; the state holds F = 8 fields (h_0, M_0, h_1, M_1) and recv is [R][8]
 } StageDesc;
 
 int stsp_stage_launch(int phys, int dtype, int bx, int by, const StageDesc* d, hipStream_t stream);
+// Two-layer shallow water (swe_layer_stage.hip): one RK stage; stsp_stage_launch routes phys 4 here.
+int stsp_swe_layer_launch(int dtype, int bx, int by, const StageDesc* d, hipStream_t stream);
+// dynamic LDS bytes of one of its blocks (-1: unsupported shape); a launch over 65536 is refused with -13
+int stsp_swe_layer_lds(int dtype, int bx, int by);
 // Pipelined streaming SSP-RK3 step (march3_kernel.hip): one launch marches all
 // three stages up each strip of a tile (stage s + 1 trails stage s by two rows),
 // reading the step input d->Q once and writing the step output d->out at the

@@ -43,6 +43,7 @@ class DerivedFields:
         # more than the four SWE fields (tracers) exchanges all of them; the kernel
         # and the twin read rows of four, so finish() copies the SWE columns over
         self.F = int(phys.F)
+        self.layer = 0          # layered shallow water: the layer whose rows 4 k .. 4 k + 3 are read
         self._recv_all = self.transport().recv
         self.recv = self._recv_all if self.F == 4 else self._recv_all.new_zeros((plan.num_recv, 4))
         if self.hip:
@@ -112,6 +113,15 @@ class DerivedFields:
         d.nblocks = self.nblocks
         d.g, d.omega2 = self.g, self.omega2
 
+    def set_layer(self, k: int) -> None:
+        """Read layer ``k`` of a layered shallow-water state (rows 4 k .. 4 k + 3
+        of the state, a contiguous slice, and the same columns of the receive
+        buffer, copied over by ``finish``).  Set before ``start()``."""
+        nl = int(getattr(self.e.physics, "nl", 1))
+        if not 0 <= int(k) < nl:
+            raise ValueError(f"derived fields of layer {k}: this run carries {nl} layer(s)")
+        self.layer = int(k)
+
     # ---- exchange -------------------------------------------------------------------
     def transport(self):
         """The transport that delivers this rank's remote ghosts outside the
@@ -134,7 +144,7 @@ class DerivedFields:
         if self.e.plan.num_recv:
             self.transport().finish()
             if self.F != 4:
-                self.recv.copy_(self._recv_all[:, :4])
+                self.recv.copy_(self._recv_all[:, 4 * self.layer:4 * self.layer + 4])
 
     # ---- compute --------------------------------------------------------------------
     def compute(self, q: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -142,7 +152,7 @@ class DerivedFields:
         (default: the engine's state) as device tensors.  The HIP path returns
         its own buffers, overwritten by the next call."""
         e = self.e
-        q = (e.state if q is None else q)[:4]      # (h, M): a contiguous view of the leading rows
+        q = (e.state if q is None else q)[4 * self.layer:4 * self.layer + 4]   # (h, M): a contiguous view of four rows
         if not self.hip:
             recv = self.recv if e.plan.num_recv else None
             return e.physics.derived(q, recv, e.gmap, e.cmap, e.tens, self.tabs, self.order, self.T, self.n,

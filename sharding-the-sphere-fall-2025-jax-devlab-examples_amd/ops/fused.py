@@ -1113,6 +1113,8 @@ def fused_supported_config(physics, integrator: str, layout: TileLayout, B: Opti
     from ..models.swe import ShallowWater
     if not isinstance(physics, ShallowWater):
         return "fused step: shallow water only"
+    if getattr(physics, "kernel_id", None) == 4:      # LayeredShallowWater: its stage kernel is swe_layer_stage.hip
+        return "fused step: no layers"
     if physics.F != 4:      # ShallowWaterTracers: its stage kernel is swe_tracer_stage.hip
         return "fused step: no tracers"
     if int(physics.limiter) not in (0, 1, 2, 3):

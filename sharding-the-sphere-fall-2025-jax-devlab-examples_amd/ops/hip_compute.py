@@ -27,7 +27,9 @@ BLOCK_SHAPES = ((16, 16), (32, 8), (16, 8), (8, 16), (8, 8))
 MARCH_SHAPES = ((64, 4), (64, 8), (64, 16), (64, 32))
 # Shallow water with tracers (physics 3, ops/csrc/swe_tracer_stage.hip)
 TRACER_SHAPES = ((16, 16), (16, 8))
-SWE_KERNELS = (2, 3)      # physics ids that read the SWE geometry (mx, my, cgeo)
+# Two-layer shallow water (physics 4, ops/csrc/swe_layer_stage.hip)
+LAYER_SHAPES = ((16, 16), (16, 8))
+SWE_KERNELS = (2, 3, 4)   # physics ids that read the SWE geometry (mx, my, cgeo)
 
 
 MARCH_AUTO = (64, 4)
@@ -195,6 +197,34 @@ def choose_tracer_block(n: int, tiles: int = 0, cus: int = 0, nq: int = 1, esize
     return (16, 8)
 
 
+LAYER_LDS_MAX = 65536     # dynamic LDS a launch gets without opting in
+
+
+def layer_lds_bytes(bx: int, by: int, esize: int = 8) -> int:
+    """Dynamic LDS of one block of the two-layer stage kernel
+    (swe_layer_stage.hip, ``LyGeom::ELEMS * sizeof(T)``; the library exports the
+    same number as ``stsp_swe_layer_lds`` and ``HipCompute`` checks the two
+    agree): a window of eight primitives and one sqrt(g H) row with 2 ghost
+    layers, five flux rows the layers share, the neighbour's edge state and raw
+    cell at panel edges (eight rows each), normals and edge lengths."""
+    ne = (bx + 1) * by + bx * (by + 1)
+    wf = (by + 4) * (bx + 4 + 1)
+    bm = max(bx, by)
+    return (9 * wf + 5 * ne + 2 * 8 * 4 * bm + 3 * (bx + by + 2) + ne) * esize
+
+
+def choose_layer_block(n: int, tiles: int = 0, cus: int = 0, esize: int = 8):
+    """Block shape of the two-layer stage kernel, among ``LAYER_SHAPES`` by the
+    rule of ``choose_tracer_block``: 16 x 16 while its grid fits the compute
+    units in one pass and the 16 x 8 grid does not (and its launch fits in
+    ``LAYER_LDS_MAX``), else 16 x 8."""
+    def count(bx, by):
+        return tiles * -(-n // bx) * -(-n // by)
+    if tiles and cus and count(16, 16) <= cus < count(16, 8) and layer_lds_bytes(16, 16, esize) <= LAYER_LDS_MAX:
+        return (16, 16)
+    return (16, 8)
+
+
 class HipCompute:
     def __init__(self, engine):
         e = engine
@@ -214,6 +244,8 @@ class HipCompute:
                 kp = phys.kernel_params()
                 bx, by = choose_tracer_block(n, T, cus, int(kp["nq"]), torch.tensor([], dtype=e.dtype).element_size(),
                                              int(kp.get("tracer_limiter", 0)))
+            elif self.phys_id == 4:
+                bx, by = choose_layer_block(n, T, cus, torch.tensor([], dtype=e.dtype).element_size())
             else:
                 bx, by = choose_block(n, T, cus, getattr(phys, "limiter", 0), torch.tensor([], dtype=e.dtype).element_size())
             # streaming stage once the rank streams: measured C720 (3.1M cells, 12k per CU)
@@ -235,6 +267,8 @@ class HipCompute:
             raise ValueError(f"unsupported block shape {(bx, by)}")
         elif self.phys_id == 3 and (bx, by) not in TRACER_SHAPES:
             raise ValueError(f"shallow water with tracers runs blocks {TRACER_SHAPES}, not {(bx, by)}")
+        elif self.phys_id == 4 and (bx, by) not in LAYER_SHAPES:
+            raise ValueError(f"two-layer shallow water runs blocks {LAYER_SHAPES}, not {(bx, by)}")
         self._shape(bx, by)
         # streaming stage geometry: compact (panel-shared tables, grad b from b) for fp64,
         # per-tile records for fp32 (C720 64x4: fp64 409 vs 415 us/step, fp32 225 vs 195,
@@ -287,6 +321,25 @@ class HipCompute:
                 raise ValueError(f"tracer stage kernel: block {(bx, by)} with {self._nq} tracers"
                                  f"{' on PPM' if self._tlim == 4 else ''} needs {lds} bytes of LDS per block, "
                                  f"more than the {TRACER_LDS_MAX} a launch gets; use block (16, 8)")
+        self._layer_r = 0.0
+        if self.phys_id == 4:      # (h_0, M_0, h_1, M_1): the kernel strides the state and the receive buffer by 8
+            kp = phys.kernel_params()
+            if int(kp["layers"]) != 2:
+                raise ValueError(f"the layer stage kernel runs two layers, not {int(kp['layers'])} "
+                                 f"(backend='torch' takes any number)")
+            assert F == 8, "two-layer state: (h, M) of each layer"
+            assert 0 <= int(kp.get("limiter", 0)) <= 3, "the layer stage kernel has the PLR limiters 0 to 3"
+            self._layer_r = float(kp["layer_r"])
+            assert 0.0 < self._layer_r <= 1.0, "layer stage kernel: density ratio rho_0 / rho_1 in (0, 1]"
+            assert plan.ng >= 2 and "pedge" in t and "pe_base" in t
+            self.lib.stsp_swe_layer_lds.argtypes = [ctypes.c_int] * 3
+            self.lib.stsp_swe_layer_lds.restype = ctypes.c_int
+            lds = int(self.lib.stsp_swe_layer_lds(self.dcode, bx, by))
+            esize = torch.tensor([], dtype=e.dtype).element_size()
+            assert lds == layer_lds_bytes(bx, by, esize), "layer stage kernel: LDS size rule"
+            if lds > LAYER_LDS_MAX:
+                raise ValueError(f"layer stage kernel: block {(bx, by)} needs {lds} bytes of LDS per block, "
+                                 f"more than the {LAYER_LDS_MAX} a launch gets; use block (16, 8)")
         assert S == T * (n + 2 * plan.ng) ** 2
         pm = plan.push_map
         assert pm.shape == (T, 4, plan.ng, n) and pm.max(initial=-1) < S
@@ -382,6 +435,7 @@ class HipCompute:
             d.mx, d.my, d.cgeo = p(t["mx"]), p(t["my"]), p(t["cgeo"])
         d.nq = self._nq
         d.tracer_limiter = self._tlim
+        d.layer_r = self._layer_r
         if "pedge" in t:
             d.pedge = p(t["pedge"])
         if "pe_base" in t:

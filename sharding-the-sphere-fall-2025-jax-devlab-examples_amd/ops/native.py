@@ -46,6 +46,8 @@ class StageDesc(ctypes.Structure):
         ("cgmap", ctypes.c_void_p), ("cpush", ctypes.c_void_p),
         # shallow water with tracers (swe_tracer_stage.hip)
         ("nq", ctypes.c_int), ("tracer_limiter", ctypes.c_int),
+        # two-layer shallow water (swe_layer_stage.hip)
+        ("layer_r", ctypes.c_double),
     ]
 
 

@@ -230,7 +230,7 @@ class XgmiHalo:
             # the granule codecs pack 1 or 4 fields; raised before anything is
             # allocated, so the solver's transport chain moves on to ipc / rccl
             raise RuntimeError(f"the direct xGMI exchange packs 1 or 4 fields, not {e.physics.F} "
-                               f"(shallow water with tracers exchanges through ipc or rccl)")
+                               f"(shallow water with tracers or layers exchanges through ipc or rccl)")
         if not isinstance(e.compute, HipCompute):
             raise RuntimeError("XgmiHalo needs an Engine with backend='hip'")
         self.e = e

@@ -69,6 +69,12 @@ class PhysicsConfig:
     # interval: steps between applications (default 1), depth: diffuse the free
     # surface too (default true; false with tracers)}; null = off
     dissipation: Optional[Dict[str, Any]] = None
+    # shallow water only: stacked (isopycnal) layers, models/swe.py::LayeredShallowWater:
+    # {depths: [H_0, H_1] resting depths from the top (m), density_ratio: rho_0 / rho_1
+    # (default 0.9), winds: [w_0, w_1] layer winds of case tc2 as fractions of TC2's u0,
+    # jet_scale: the Galewsky wind's factor in layered_jet (default 0.25)}; cases tc2 |
+    # rest | tc5 | layered_jet | layered_jet_balanced; null = one homogeneous layer
+    layers: Optional[Dict[str, Any]] = None
 
 
 @dataclass
