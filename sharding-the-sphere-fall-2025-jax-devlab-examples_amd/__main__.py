@@ -26,8 +26,9 @@
                                                        back on the cells (--band: degrees LMIN .. LCUT only), or
                                                        the streamfunction / velocity_potential of a
                                                        shallow-water history, on the CPU
-    ensemble CONFIG.yaml [--members M] [--amplitude A] [--days D | --nsteps K]
+    ensemble CONFIG.yaml [--members M] [--amplitude A] [--days D | --nsteps K] [--batched]
                                                        perturbed members of one config on one device
+                                                       (--batched: every member's stage in one launch)
     build                                              compile the gfx950 library
 """
 import argparse
@@ -95,6 +96,8 @@ def main(argv=None):
     en.add_argument("--amplitude", type=float, default=1e-4)
     en.add_argument("--days", type=float)
     en.add_argument("--nsteps", type=int)
+    en.add_argument("--batched", action="store_true",
+                    help="batched storage: one stage launch steps every member (Ensemble mode='batched')")
     sub.add_parser("build")
     a = ap.parse_args(argv)
 
@@ -170,7 +173,8 @@ def main(argv=None):
         print(json.dumps({"out": a.out, "field": a.field, "shape": list(r["field"].shape)}))
         return 0
     if a.cmd == "ensemble":
-        print(json.dumps(run_ensemble(a.config, a.members, a.amplitude, a.days, a.nsteps), default=float))
+        print(json.dumps(run_ensemble(a.config, a.members, a.amplitude, a.days, a.nsteps, batched=a.batched),
+                         default=float))
         return 0
     from .utils.config import load_config
     if a.cmd == "run" and load_config(a.config).physics.model == "planar_swe":
@@ -381,9 +385,10 @@ def synth_history(history: str, field: str, lmax: int, band=None) -> dict:
     return {"field": torch.stack(out).numpy(), "time": zarr_lite.read_array(history, "time")}
 
 
-def run_ensemble(config, members: int, amplitude: float, days=None, nsteps=None) -> dict:
+def run_ensemble(config, members: int, amplitude: float, days=None, nsteps=None, *, batched: bool = False) -> dict:
     """``members`` perturbed copies of a run configuration stepped together
-    on one device (``stsphere.Ensemble``); returns throughput and spread."""
+    on one device (``stsphere.Ensemble``; ``batched``: its mode 'batched', one
+    stage launch for all members); returns throughput and spread."""
     import math
     import time
     import torch
@@ -391,7 +396,7 @@ def run_ensemble(config, members: int, amplitude: float, days=None, nsteps=None)
     from .models.geometry import DAY
     from .utils.config import load_config
     c = load_config(config)
-    ens = Ensemble.from_config(c, members, amplitude=amplitude)
+    ens = Ensemble.from_config(c, members, amplitude=amplitude, mode="batched" if batched else "streams")
     if nsteps is None:
         d = days if days is not None else c.time.days
         nsteps = int(math.ceil(d * DAY / ens.dt - 1e-9)) if d is not None else (c.time.nsteps or 1)
@@ -406,7 +411,7 @@ def run_ensemble(config, members: int, amplitude: float, days=None, nsteps=None)
     after = ens.spread()
     ens.close()
     cells = 6 * c.grid.N ** 2
-    return {"members": members, "steps": nsteps, "dt": ens.dt, "wall_s": wall,
+    return {"members": members, "mode": ens.mode, "steps": nsteps, "dt": ens.dt, "wall_s": wall,
             "aggregate_cell_updates_per_s": members * cells * nsteps / max(wall, 1e-12),
             "native": ens.native, "field0_mean": after["mean"], "field0_spread_rms_initial": before["spread_rms"],
             "field0_spread_rms_final": after["spread_rms"]}

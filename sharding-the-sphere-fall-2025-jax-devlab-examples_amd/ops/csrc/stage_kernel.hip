@@ -893,6 +893,98 @@ int launch_d(int phys, int bx, int by, const StageDesc* d, hipStream_t s) {
   return -3;
 }
 
+// ---- batched entry: one stage of `members` independent states in one launch ----
+// Member m runs stage_body on X, Q, acc_in, out, acc_out advanced by m * stride
+// elements; the geometry, the maps and the scalars are shared, so the members'
+// blocks read the same table lines.
+//
+// Placement.  Workgroups are dealt round-robin over the 8 XCDs by linear id, and
+// xcd_remap gives XCD x the logical blocks [start(x), start(x) + c(x)), c(x) = the
+// ids below nblocks that are congruent to x mod 8.  The batched grid is 1-D with
+// 8 * members * ceil(nblocks / 8) workgroups; workgroup `lin` sits on XCD x = lin & 7
+// and is that XCD's j-th (j = lin >> 3).  j = k * members + m: member m, and the
+// XCD's k-th block, i.e. id k * 8 + x of a one-member launch, remapped as there.
+// So (a) logical block b of every member runs on the XCD that runs it in a
+// one-member launch (they share its geometry lines, and a member's neighbouring
+// blocks still share an L2), whatever nblocks % 8 is, (b) for each member the
+// ids k * 8 + x < nblocks are each taken once, so its remap is the bijection of
+// xcd_remap, and (c) the members of one block are adjacent in dispatch order.  The
+// workgroups with k * 8 + x >= nblocks (at most 7 per member, only when nblocks % 8
+// != 0) leave at once.  Correctness does not depend on where a workgroup runs.
+template <typename T, int P, int BX, int BY, int LIM>
+__global__ __launch_bounds__((Geom<BX, BY>::NT)) __attribute__((amdgpu_waves_per_eu(StageOcc<BX, BY>::WPE)))
+void stage_batch_kernel(Args<T> a, int members, unsigned mdiv_m, long long stride) {
+  pin_args(a);
+  const int lin = blockIdx.x;
+  const int xcd = lin & 7, j = lin >> 3;
+  const int k = mdiv_m ? (int)__umulhi((unsigned)j, mdiv_m) : j / members;
+  const int m = j - k * members;
+  const int orig = k * 8 + xcd;
+  if (orig >= a.nblocks) return;      // workgroup-uniform, before any barrier
+  Args<T> b = a;
+  const long long off = (long long)m * stride;
+  b.X += off;
+  b.Q += off;
+  b.out += off;
+  if (b.acc_in) b.acc_in += off;
+  if (b.acc_out) b.acc_out += off;
+  b.stamps = nullptr;                 // the stamp rows are indexed by blockIdx of a one-member grid
+  stage_body<T, P, BX, BY, LIM, false, false, false>(b, xcd_remap(orig, a.nblocks));
+}
+
+template <typename T, int P, int BX, int BY, int LIM>
+int launch_bl(const StageDesc* d, int members, long long stride, hipStream_t s) {
+  Args<T> a = make_args<T>(d);
+  set_magic<T, BX, BY>(a);
+  a.wt = want_wt((long)members * d->nblocks * BX * BY) ? 1 : 0;   // the cells of the whole launch
+  a.pew = (d->n % BX == 0 && d->n % BY == 0) ? 1 : 0;
+  const unsigned rows = ((unsigned)d->nblocks + 7u) / 8u;          // blocks per XCD, rounded up
+  const unsigned mdiv_m = magic_div((unsigned)members, (unsigned long long)rows * (unsigned)members);
+  const dim3 grid(8u * rows * (unsigned)members), block(Geom<BX, BY>::NT);
+  hipLaunchKernelGGL((stage_batch_kernel<T, P, BX, BY, LIM>), grid, block, 0, s, a, members, mdiv_m, stride);
+  return (int)hipGetLastError();
+}
+
+template <typename T, int P, int BX, int BY>
+int launch_bt(const StageDesc* d, int members, long long stride, hipStream_t s) {
+  if (d->pw != d->n + 2 * d->mg || d->mg < Phys<P>::NG || (d->limiter == 4 && d->mg < 3)) return -5;
+  if (P != 1 && (!d->pedge || !d->pe_base || !d->pe_t || d->n < 2)) return -12;
+  if (!d->push) return -6;
+  if constexpr (P == 1) return launch_bl<T, P, BX, BY, 0>(d, members, stride, s);
+  switch (d->limiter) {
+    case 0: return launch_bl<T, P, BX, BY, 0>(d, members, stride, s);
+    case 1: return launch_bl<T, P, BX, BY, 1>(d, members, stride, s);
+    case 2: return launch_bl<T, P, BX, BY, 2>(d, members, stride, s);
+    case 3: return launch_bl<T, P, BX, BY, 3>(d, members, stride, s);
+    case 4:
+      if constexpr ((BX + 6) * (BY + 6) <= Geom<BX, BY>::NT) return launch_bl<T, P, BX, BY, 4>(d, members, stride, s);
+      else return -11;
+  }
+  return -7;
+}
+
+template <typename T, int P>
+int launch_bp(int bx, int by, const StageDesc* d, int members, long long stride, hipStream_t s) {
+  if (stride < (long long)Phys<P>::F * d->S) return -21;
+  if (d->nblocks <= 0) return 0;
+  if (bx == 16 && by == 16) return launch_bt<T, P, 16, 16>(d, members, stride, s);
+  if (bx == 32 && by == 8) return launch_bt<T, P, 32, 8>(d, members, stride, s);
+  if (bx == 16 && by == 8) return launch_bt<T, P, 16, 8>(d, members, stride, s);
+  if (bx == 8 && by == 16) return launch_bt<T, P, 8, 16>(d, members, stride, s);
+  if (bx == 8 && by == 8) return launch_bt<T, P, 8, 8>(d, members, stride, s);
+  return -2;
+}
+
+template <typename T>
+int launch_bd(int phys, int bx, int by, const StageDesc* d, int members, long long stride, hipStream_t s) {
+  switch (phys) {
+    case 0: return launch_bp<T, 0>(bx, by, d, members, stride, s);
+    case 1: return launch_bp<T, 1>(bx, by, d, members, stride, s);
+    case 2: return launch_bp<T, 2>(bx, by, d, members, stride, s);
+  }
+  return -3;
+}
+
 // ---- pack: send[k][f] = q[f][idx[k]] ----------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void pack_kernel(const T* __restrict__ q, int S, int F, const int* __restrict__ idx,
@@ -943,6 +1035,20 @@ extern "C" int stsp_stage_launch(int phys, int dtype, int bx, int by, const Stag
   if (dtype == 1) return launch_d<double>(phys, bx, by, d, stream);
   if (dtype == 0) return launch_d<float>(phys, bx, by, d, stream);
   return -4;
+}
+
+// The same stage of `members` states in one launch (codes: stsp_kernels.h); every
+// check comes before the launch
+extern "C" int stsp_stage_batch_launch(int phys, int dtype, int bx, int by, const StageDesc* d, int members,
+                                       long long member_stride, hipStream_t stream) {
+  if (phys == 3 || phys == 4) return -3;
+  if (bx == 64) return -2;
+  if (dtype != 0 && dtype != 1) return -4;
+  const long long rows = d->nblocks > 0 ? ((long long)d->nblocks + 7) / 8 : 0;
+  if (members < 1 || 8 * rows * members > 0x7fffffffLL) return -20;
+  if (d->remote || d->blocks || d->xg) return -22;
+  if (dtype == 1) return launch_bd<double>(phys, bx, by, d, members, member_stride, stream);
+  return launch_bd<float>(phys, bx, by, d, members, member_stride, stream);
 }
 
 extern "C" int stsp_pack_launch(int dtype, const void* q, int S, int F, const int* idx, int ns, void* send,

@@ -79,6 +79,19 @@ typedef struct StageDesc {
 } StageDesc;
 
 int stsp_stage_launch(int phys, int dtype, int bx, int by, const StageDesc* d, hipStream_t stream);
+// One RK stage of `members` independent states in one launch (stage_kernel.hip,
+// stage_batch_kernel; ensemble.py mode="batched").  Member m works on X, Q,
+// acc_in, out and acc_out advanced by m * member_stride elements (null acc_in /
+// acc_out stay null); every other pointer and scalar of the descriptor is shared.
+// d->nblocks is the block count of ONE member.  Physics 0, 1, 2 and the five block
+// shapes of the plain stage kernel; the codes of stsp_stage_launch apply (bx == 64:
+// -2, physics 3 / 4: -3, dtype: -4, ...), and nothing is launched on any of them or on
+//   -20  members < 1, or more members than one launch holds
+//        (8 * members * ceil(nblocks / 8) workgroups must stay below 2^31)
+//   -21  member_stride < F * S (members would overlap)
+//   -22  a descriptor with remote, blocks or xg set (one rank, all blocks, no exchange)
+int stsp_stage_batch_launch(int phys, int dtype, int bx, int by, const StageDesc* d, int members,
+                            long long member_stride, hipStream_t stream);
 // Two-layer shallow water (swe_layer_stage.hip): one RK stage; stsp_stage_launch routes phys 4 here.
 int stsp_swe_layer_launch(int dtype, int bx, int by, const StageDesc* d, hipStream_t stream);
 // dynamic LDS bytes of one of its blocks (-1: unsupported shape); a launch over 65536 is refused with -13
@@ -400,6 +413,25 @@ typedef struct HeatDesc {
 } HeatDesc;
 int stsp_heat_launch(int dtype, const HeatDesc* d, hipStream_t stream);
 int stsp_heat_desc_size(void);
+// Ensemble statistics of one field of a batched state (ensemble_kernel.hip,
+// ops/ensemble_stats.py; definitions and the twin in models/ensemble_stats.py):
+// a launch with one workgroup per 16 x 16 cell block (mean and population
+// variance over the members per cell, in float64, and a block record), then a
+// one-workgroup fold of the records in ascending block order.
+typedef struct EnsStatsDesc {
+  const void* Q;        // [members][fields][S] batched state (element type), padded layout; interior cells are read
+  const void* area;     // [T][n][n] cell areas (element type)
+  double* mean;         // [T][n][n] out
+  double* var;          // [T][n][n] out
+  double* partials;     // [nblocks][4] block records: sum A mean, sum A var, sum A, max var
+  double* out;          // [4] out: the records folded
+  long long member_stride;  // elements between members, >= fields * S
+  int members, fields, field;
+  int ntile, n, S, mg, pw;  // as StageDesc
+  int nblocks;          // ntile * ceil(n / 16)^2
+} EnsStatsDesc;
+int stsp_ensemble_stats_launch(int dtype, const EnsStatsDesc* d, hipStream_t stream);
+int stsp_ensemble_stats_desc_size(void);
 // Direct xGMI halo build constant: ring slots.
 int stsp_xg_slots(void);
 }

@@ -207,6 +207,9 @@ def load(build_if_missing: bool = True):
             if size(*args) != ctypes.sizeof(cls):
                 raise RuntimeError(f"{cls.__name__}: ctypes mirror is {ctypes.sizeof(cls)} bytes, "
                                    f"the library's {size(*args)} (stale libstsp.so?)")
+        # the batched stage: (phys, dtype, bx, by, desc, members, member_stride, stream)
+        L.stsp_stage_batch_launch.argtypes = [ci, ci, ci, ci, _P(StageDesc), ci, ctypes.c_longlong, vp]
+        L.stsp_stage_batch_launch.restype = ci
         _declare_runtime(L)
         _declare_tt(L)
         L.stsp_schedule_spin.argtypes = [ci]
