@@ -122,6 +122,14 @@ struct FD {
   static_assert(2 * (B + 4 * (NS - 2)) * (B + 4 * (NS - 2) + 1) <= 32 * 64 && 2 * H1 * (H1 + 1) <= 32 * 64 + 64 * 64,
                 "face passes per stage fit the 32-entry pass table");
   static constexpr int CMAX = 32;
+  // face task table of a block (PFN builds; ops/fused.py::face_tables): per
+  // stage the passes of the arithmetic mapping and two more (a shared pass
+  // holds at most 63 faces, and shared and full faces do not mix in a pass)
+  static constexpr int cdiv64(int x) { return (x + 63) / 64; }
+  static constexpr int TCAP = cdiv64(2 * (H1 * (H1 + 1) - (B - 3) * B)) + 2 +
+                              (NS > 1 ? cdiv64(2 * (B + 4 * (NS - 2)) * (B + 4 * (NS - 2) + 1)) + 2 : 0) +
+                              (NS > 2 ? cdiv64(2 * (B + 4 * (NS - 3)) * (B + 4 * (NS - 3) + 1)) + 2 : 0);
+  static_assert(NS <= 3, "TCAP sums three stages");
 };
 
 // region of extended-panel coordinates: 0 P, 1 W, 2 E, 3 S, 4 N, -1 none
@@ -255,8 +263,12 @@ struct FArgs {
   int nsteps;
   const int* prod;        // [nb][PM] producer blocks, -1 padded
   int PM;
-  const unsigned* sched;  // [nb][3 stages][17]: per wave (16) bit p = the wave runs face pass p (faces 64 p ..
-                          // 64 p + 63); word 16 bit p = pass p holds a face next to a panel-edge line
+  const unsigned* sched;  // [nb][3 stages][20]: per wave (16) bit p = the wave runs face pass p (faces 64 p ..
+                          // 64 p + 63); word 16 bit p = pass p holds a face next to a panel-edge line;
+                          // PFN builds: word 17 bit p = pass p is a shared pass, word 18 the stage's
+                          // first pass in the block's task table, word 19 the table's row in ftab
+  const unsigned short* ftab;   // [classes][64 TCAP] face tasks of every pass slot (PFN builds): fu (5 bits),
+                          // fv (5), axis (1), kind (2: 0 idle, 1 shared face, 2 full face, 3 slope only)
   const T* nrmf;          // [nb][3][NFL] per-face normals of panel-edge blocks (PFN builds)
   // tagged in-launch hand-off (several steps per launch; null = the epoch
   // hand-off): [2 slots][HX<T>::W words][S] u64, word-major.  At the end of
@@ -405,6 +417,21 @@ __device__ __forceinline__ int sel5(int r, int v0, int v1, int v2, int v3, int v
   return r == 0 ? v0 : r == 1 ? v1 : r == 2 ? v2 : r == 3 ? v3 : v4;
 }
 
+// the value the next lane of the wave holds (lane 63 keeps its own): DPP
+// wave_shl:1, one v_mov_dpp per 32 bits, every lane of the wave active
+template <typename T>
+__device__ __forceinline__ T next_lane(T v) {
+  if constexpr (sizeof(T) == 8) {
+    int2 p = __builtin_bit_cast(int2, v);
+    p.x = __builtin_amdgcn_update_dpp(p.x, p.x, 0x130, 0xF, 0xF, false);
+    p.y = __builtin_amdgcn_update_dpp(p.y, p.y, 0x130, 0xF, 0xF, false);
+    return __builtin_bit_cast(T, p);
+  } else {
+    const int x = __builtin_bit_cast(int, v);
+    return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(x, x, 0x130, 0xF, 0xF, false));
+  }
+}
+
 // neighbour code of a window cell on one side (-1 window neighbour, >= 0 ghost
 // entry, -3 no cell)
 __device__ __forceinline__ int ncode(unsigned long long c, int side) {
@@ -450,6 +477,8 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
   constexpr int NX2 = NS > 1 ? (B + 4 * (NS - 2)) * (B + 4 * (NS - 2)) : 1;
   __shared__ T s_x[4][NX2];
   __shared__ int s_gdone;                  // ghost waves done, cumulative over the launch's stages
+  constexpr int NTB = PFN ? 64 * D::TCAP : 2;
+  __shared__ unsigned short s_tab[NTB];    // PFN: the block class's face task table (FArgs::ftab)
 
   const int tid = threadIdx.x;
   const int bid = xcd_remap(blockIdx.x, a.nblocks);
@@ -534,11 +563,15 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
   }
   // this wave's face passes per stage (bit p: faces 64 p .. 64 p + 63), in SGPRs
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  unsigned pmask[3], nmask[3];
+  unsigned pmask[3], nmask[3], smask[3];
+  int tb[3];                                             // PFN: the stage's first pass in s_tab
 #pragma unroll
   for (int s = 0; s < 3; ++s) {
-    pmask[s] = __builtin_amdgcn_readfirstlane(a.sched[((long)bid * 3 + s) * 17 + wv]);
-    nmask[s] = __builtin_amdgcn_readfirstlane(a.sched[((long)bid * 3 + s) * 17 + 16]);
+    const unsigned* sw = a.sched + ((long)bid * 3 + s) * 20;
+    pmask[s] = __builtin_amdgcn_readfirstlane(sw[wv]);
+    nmask[s] = __builtin_amdgcn_readfirstlane(sw[16]);
+    smask[s] = PFN ? __builtin_amdgcn_readfirstlane(sw[17]) : 0u;
+    tb[s] = PFN ? __builtin_amdgcn_readfirstlane(sw[18]) : 0;
   }
   // face lengths of the stage-1 face set: region of the face's lower cell (else
   // upper), its panel-local edge through the region map, the shared length table
@@ -728,6 +761,12 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
       if (j < 3 * NFL) s_nrmf[j] = nfv[k];
     }
   }
+  if constexpr (PFN) {
+    // this block's face task table, two slots per word (once per launch, after
+    // the other tables: no registers held across the prologue's loads)
+    const unsigned* tp = (const unsigned*)a.ftab + (long)a.sched[(long)bid * 3 * 20 + 19] * (NTB / 2);
+    for (int j = tid; j < NTB / 2; j += NT) ((unsigned*)s_tab)[j] = tp[j];
+  }
   if (edge) {
     if (owner) s_code[v * CS + u] = cdv;
     if (tid < a.G) { s_gs[tid][0] = (short)gs0; s_gs[tid][1] = (short)gs1; s_gt[tid] = gtv; }
@@ -843,6 +882,50 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
 #pragma unroll
     for (int f = 0; f < 4; ++f) s_fl[f][fslot] = fl[f];
   };
+  // The shared form of MODE 0 / MODE 1 (PFN builds, passes the host flags as
+  // shared; ops/fused.py::face_table): a lane computes the limited slope of
+  // its lower cell only and takes that of its upper cell from the next lane,
+  // which holds the next face line of the same row or, at the end of a run,
+  // the slope-only task of that cell.  The next lane's operands are this
+  // lane's (cr - cl, bp - cr) in the same order, so every flux is bit for bit
+  // the full body's.  No face of a shared pass is next to a panel-edge line:
+  // no codes, no ghost wait.  Every lane of the wave runs up to the exchange;
+  // lanes without a flux (slope only, idle) leave after it.
+  auto face_shared = [&](bool ax, int fu, int fv, int k, bool flux, auto mode_c) {
+    constexpr int MODE = decltype(mode_c)::value;
+    const int st = ax ? WS : 1;
+    int fslot = ax ? NFX + (k - L1) * H1 + (fu - L1) : (fv - L1) * (H1 + 1) + (k - L1);
+    fslot = flux ? fslot : 0;
+    const int ib = fv * WS + fu, ia = ib - st, iam = ia - st;
+    T cl[5], cr[5], hsa[4], hsb[4];
+#pragma unroll
+    for (int f = 0; f < 5; ++f) { cl[f] = wf[f * WW + ia]; cr[f] = wf[f * WW + ib]; }
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      const T am = wf[f * WW + iam];
+      hsa[f] = half_slope<LIM>(cl[f] - am, cr[f] - cl[f]);
+    }
+#pragma unroll
+    for (int f = 0; f < 4; ++f) hsb[f] = next_lane(hsa[f]);
+    if (!flux) return;
+    T wl[4], wr[4];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      wl[f] = cl[f] + hsa[f];
+      wr[f] = cr[f] - hsb[f];
+    }
+    T m0, m1, m2;
+    if constexpr (MODE != 0) {                             // per-face normal (edge block)
+      m0 = s_nrmf[fslot]; m1 = s_nrmf[NFL + fslot]; m2 = s_nrmf[2 * NFL + fslot];
+    } else {                                               // line normal of the panel
+      const T* m = &s_nrm[ax ? 1 : 0][0][0][k];
+      m0 = m[0]; m1 = m[W + 1]; m2 = m[2 * (W + 1)];
+    }
+    T fl[4];
+    swe_flux<T>(wl, wr, cl, cr, m0, m1, m2, s_len[fslot], a.g, fl);
+#pragma unroll
+    for (int f = 0; f < 4; ++f) s_fl[f][fslot] = fl[f];
+  };
   // Stage-1 faces whose whole stencil lies in the block's own cells ("inner":
   // lines k in [R+2, R+B-2] x the block's B rows, both axes): a multi-step
   // launch computes them while it waits for its producers (the own cells'
@@ -900,7 +983,9 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
   __syncthreads();
   if (wait && !tagh && !pcell && tid < 64) {
     // wait for the producers' previous step (wave 0 polls) ...
-    const int p = tid < a.PM ? a.prod[(long)bid * a.PM + tid] : -1;
+    int pt = tid;
+    asm volatile("" : "+v"(pt));             // per step: no address held in registers across the steps
+    const int p = tid < a.PM ? a.prod[(long)bid * a.PM + pt] : -1;
     const int pa = p >= 0 ? p : bid;
     // (the error word is read after a failed poll, xg_spin; reading it with
     // the counters in one round trip made no measurable difference at C96,
@@ -951,7 +1036,9 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
         // this thread's window cells: wait for each one's producer to have
         // completed the previous step (a wave's lanes share a few producers)
         auto poll_prod = [&](int cu, int cv) {
-          const int k = a.pidx[(long)bid * W * W + cv * W + cu];
+          int ci = cv * W + cu;
+          asm volatile("" : "+v"(ci));       // per step: no address held in registers across the steps
+          const int k = a.pidx[(long)bid * W * W + ci];
           if (k < 0) return;
           const int p = a.prod[(long)bid * a.PM + k];
           int e = 0;
@@ -1022,7 +1109,7 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
     unsigned m = pmask[s];
     for (int first = (ncor && wv == 0) ? 1 : 0; first || m;) {
       int task;
-      bool nearp = false;
+      bool nearp = false, sharep = false;
       if (first) {                                          // the corner wave's cube-corner faces
         task = (tid & 63) - 64;
         first = 0;
@@ -1030,10 +1117,29 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
         const int pp = __builtin_ctz(m);
         task = pp * 64 + (tid & 63);
         nearp = (nmask[s] >> pp) & 1u;
+        sharep = (smask[s] >> pp) & 1u;
         m &= m - 1u;
       }
-      if (task >= ntask) continue;
-      if (task >= 0) {
+      if (!PFN && task >= ntask) continue;
+      if (PFN && task >= 0) {
+        // table-driven pass: the slot's task from the block class's table.  The
+        // body follows the pass's flags (wave-uniform), never a lane's kind
+        const unsigned e = s_tab[tb[s] * 64 + task];
+        const int fu = e & 31, fv = (e >> 5) & 31, kind = (e >> 11) & 3;
+        const bool ax = (e >> 10) & 1;
+        const int k = ax ? fv : fu;
+        if (sharep) {
+          if (edge || STSP_FPROBE_ALLEDGE) face_shared(ax, fu, fv, k, kind == 1, std::integral_constant<int, 1>{});
+          else face_shared(ax, fu, fv, k, kind == 1, std::integral_constant<int, 0>{});
+        } else if (kind == 2) {
+          if (edge || STSP_FPROBE_ALLEDGE) {
+            if (!nearp) face(ax, fu, fv, k, std::integral_constant<int, 1>{});
+            else face(ax, fu, fv, k, std::integral_constant<int, 2>{});
+          } else {
+            face(ax, fu, fv, k, std::integral_constant<int, 0>{});
+          }
+        }
+      } else if (task >= 0) {
         const int tf = task;
         const bool ax = tf >= nax;                           // false: x-face, true: y-face
         const int t2 = ax ? tf - nax : tf;
@@ -1169,7 +1275,8 @@ __global__ __launch_bounds__((FD<NS, B>::NT)) void fused_step_kernel(FArgs<T> a)
     }
     if (last) {              // ghost slots of neighbouring tiles: for readers after the launch
       const int n = a.n, mg = a.mg;
-      const int x = xo + u - R, y = yo + v - R;              // tile-local
+      int x = xo + u - R, y = yo + v - R;                    // tile-local
+      asm volatile("" : "+v"(x), "+v"(y));   // once per launch: keep the push addresses out of registers
       const int* pm = a.push + (long)tile * 4 * mg * n;
       int pt[4] = {-1, -1, -1, -1};
       if (x < mg) pt[0] = pm[(0 * mg + x) * n + y];
@@ -1256,7 +1363,8 @@ int launch_fused(const FusedDesc* d, hipStream_t s) {
   a.nrmf = (const T*)d->nrmf;
   a.hx = (unsigned long long*)d->hx;
   a.pidx = d->pidx;
-  if (!a.sched || !a.nrmf) return -4;
+  a.ftab = (const unsigned short*)d->ftab;
+  if (!a.sched || !a.nrmf || !a.ftab) return -4;
   if (a.nsteps > 1 && (!a.prod || a.PM <= 0 || a.PM > 64 || !d->epoch || !d->err)) return -7;
   a.mdiv_n = magic_div((unsigned)d->n, (unsigned long long)d->N + 1);
   if (d->xg && (!d->recv || !d->peer_ring || !d->xpush || !d->epoch || !d->err || d->ring <= 0 ||
@@ -1380,6 +1488,19 @@ extern "C" int stsp_fused_prime_launch(int dtype, const void* q, int S, const in
   else
     return -4;
   return (int)hipGetLastError();
+}
+
+// passes in a block's face task table at block size B (FD::TCAP), 0: no such build
+extern "C" int stsp_fused_table_passes(int B) {
+  switch (B) {
+    case 6: return FD<3, 6>::TCAP;
+    case 8: return FD<3, 8>::TCAP;
+    case 12: return FD<3, 12>::TCAP;
+    case 16: return FD<3, 16>::TCAP;
+    case 18: return FD<3, 18>::TCAP;
+    case 20: return FD<3, 20>::TCAP;
+    default: return 0;
+  }
 }
 
 // 1 if this library carries the tagged in-launch hand-off

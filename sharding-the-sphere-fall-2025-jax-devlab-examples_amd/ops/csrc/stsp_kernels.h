@@ -177,7 +177,7 @@ typedef struct FusedDesc {
   const int* prod;
   int PM;
   const int* cpush;     // [T][4][mg][mg] carried corner ghost pushes (StageDesc::cpush), nullable
-  // face-pass schedule (ops/fused.py::pass_schedule): [nb][3 stages][17] u32:
+  // face-pass schedule (ops/fused.py::pass_schedule): [nb][3 stages][20] u32:
   // per wave (16) bit p set = the wave runs pass p (faces 64 p .. 64 p + 63) of
   // the stage, balanced over the CU's four SIMDs (waves w and w + 4 share one);
   // word 16 bit p = pass p holds a face next to a panel-edge line
@@ -190,10 +190,15 @@ typedef struct FusedDesc {
   // index into prod[b] of the producer of each window cell (-1: none); null =
   // wave 0 polls every producer before a barrier
   const signed char* pidx;
+  // face tasks of the table-driven builds (fp32, or B <= 16): [classes][64 TCAP]
+  // u16 per pass slot; sched words 17-19 say which passes are shared, where a
+  // stage starts and which row a block reads (ops/fused.py::face_tables)
+  const unsigned short* ftab;
 } FusedDesc;
 int stsp_fused_launch(int dtype, const FusedDesc* d, hipStream_t stream);
 int stsp_fused_limits(int* gmax, int* cmax);
 int stsp_fused_tagh(void);
+int stsp_fused_table_passes(int B);
 // the fused step's packed cell records (granules per cell) and their initial
 // delivery into the peers' xGMI rings
 int stsp_fused_record_words(int dtype);

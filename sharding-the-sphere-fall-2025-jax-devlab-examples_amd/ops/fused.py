@@ -930,6 +930,34 @@ def stage_face_counts(B: int, ns: int = 3) -> List[int]:
 PASS_SLOTS = 32    # face passes per stage in the kernel's table
 
 
+def _balance_passes(npasses: List[int], nw: int, cw: int, gw: int, weights: str,
+                    loads: Optional[List[List[int]]] = None) -> np.ndarray:
+    """[stages, PASS_SLOTS] uint8: the wave of every face pass of a block with
+    ``cw`` corner waves and ``gw`` ghost waves (``pass_schedule``'s rule).
+    ``loads``: per stage the load of each pass in quarter passes (default 4)."""
+    tab = np.zeros((len(npasses), PASS_SLOTS), dtype=np.uint8)
+    for s, npass in enumerate(npasses):
+        assert npass <= PASS_SLOTS
+        if weights == "legacy":
+            first = nw - cw
+            for p in range(npass):
+                tab[s, p] = p + cw if p < first else cw + gw + (p - first) % (nw - cw - gw)
+            continue
+        wc, wg = (int(x) for x in weights.split(":")[:2])
+        wl = [0] * nw
+        if cw:
+            wl[0] += wc
+        for w in range(cw, cw + gw):
+            wl[w] += wg
+        for p in range(npass):
+            gl = [sum(wl[w] for w in range(g, nw, 4)) for g in range(4)]
+            g = min(range(4), key=lambda g_: (gl[g_], g_))
+            w = min(range(g, nw, 4), key=lambda w_: (wl[w_], w_))
+            tab[s, p] = w
+            wl[w] += loads[s][p] if loads is not None else 4
+    return tab
+
+
 def pass_schedule(B: int, ncorner: np.ndarray, edge: np.ndarray, G: int, ns: int = 3,
                   weights: Optional[str] = None) -> np.ndarray:
     """[nb, ns, PASS_SLOTS] uint8: the wave that runs face pass p (faces 64 p
@@ -963,27 +991,7 @@ def pass_schedule(B: int, ncorner: np.ndarray, edge: np.ndarray, G: int, ns: int
         gw = ngw if edge[b] else 0
         key = (cw, gw)
         if key not in cache:
-            tab = np.zeros((ns, PASS_SLOTS), dtype=np.uint8)
-            for s, nt_s in enumerate(counts):
-                npass = -(-nt_s // 64)
-                assert npass <= PASS_SLOTS
-                if weights == "legacy":
-                    first = nw - cw
-                    for p in range(npass):
-                        tab[s, p] = p + cw if p < first else cw + gw + (p - first) % (nw - cw - gw)
-                    continue
-                wc, wg = (int(x) for x in weights.split(":"))
-                wl = [0] * nw
-                if cw:
-                    wl[0] += wc
-                for w in range(cw, cw + gw):
-                    wl[w] += wg
-                for p in range(npass):
-                    gl = [sum(wl[w] for w in range(g, nw, 4)) for g in range(4)]
-                    g = min(range(4), key=lambda g_: (gl[g_], g_))
-                    w = min(range(g, nw, 4), key=lambda w_: (wl[w_], w_))
-                    tab[s, p] = w
-                    wl[w] += 4
+            tab = _balance_passes([-(-c // 64) for c in counts], nw, cw, gw, weights)
             cache[key] = tab
         out[b] = cache[key]
     return out
@@ -1099,6 +1107,198 @@ def face_normals(P: "FusedPlan", flags: np.ndarray) -> np.ndarray:
         ra = np.where(ra < 0, 0, ra)
         out[b] = P.nrm[b, ax, ra, k, :].T
     return out
+
+
+# ---- face task tables (PFN builds of fused_step.hip) -----------------------------
+# After the producer wait a PFN build takes every face task of a pass from a
+# table: one uint16 per slot of every 64-slot pass, per block class and stage.
+# Entry: fu (bits 0-4), fv (5-9), axis (10), kind (11-12).  A *shared* face
+# computes the limited slope of its lower cell only and takes the slope of its
+# upper cell from the next lane, which holds face (ax, k + 1, p) of the same
+# row or, at the end of a run, the *slope-only* task of that cell, written as
+# the face (ax, k + 1, p) whose lower cell it is.  A *full* face is the body
+# that computes both slopes (every face next to a panel-edge line; all faces
+# with STSP_FUSED_SHARE=0, in the order of ``stage_face_coords``).
+FT_IDLE, FT_SHARED, FT_FULL, FT_SLOPE = 0, 1, 2, 3
+FT_MIN_RUN = 3          # shorter runs stay full faces (a one-face run would cost two lanes)
+SHARE_LOADS = (3, 6)    # pass_loads: a shared pass, a near pass (quarter passes; profiles/face_share)
+SCHED_WORDS = 20        # FArgs::sched per (block, stage): 16 wave masks, near, shared, table offset, class
+
+
+def ft_pack(ax, fu, fv, kind):
+    return (np.asarray(fu) | (np.asarray(fv) << 5) | (np.asarray(ax) << 10) | (np.asarray(kind) << 11)).astype(np.uint16)
+
+
+def ft_unpack(e):
+    """(ax, k, p, kind) of table entries."""
+    e = np.asarray(e).astype(np.int64)
+    fu, fv, ax, kind = e & 31, (e >> 5) & 31, (e >> 10) & 1, (e >> 11) & 3
+    return ax, np.where(ax == 1, fv, fu), np.where(ax == 1, fu, fv), kind
+
+
+def share_enabled() -> bool:
+    """STSP_FUSED_SHARE=0: every table slot a full face in the order of
+    ``stage_face_coords`` (the arithmetic of the kernel before the tables)."""
+    return os.environ.get("STSP_FUSED_SHARE", "1") != "0"
+
+
+def fused_pfn(B: int, fp32: bool) -> bool:
+    """fused_step.hip PFN: the builds whose face passes are table-driven."""
+    return fp32 or B <= 16
+
+
+def block_class(flags: int) -> Tuple[int, int]:
+    """(x, y) edge configuration of a block from its region flags (W 2, E 4,
+    S 8, N 16): per axis 0 none, 1 low, 2 high, 3 both."""
+    return (int(flags) >> 1) & 3, (int(flags) >> 3) & 3
+
+
+def class_edge_lines(B: int, cls: Tuple[int, int], ns: int = 3) -> Tuple[List[int], List[int]]:
+    """Window lines of the panel edges of a block class, per axis: the low
+    edge is the block's own low side (line R), the high edge line R + B."""
+    R = 2 * ns
+    return tuple([R + B * j for j in range(2) if c >> j & 1] for c in cls)
+
+
+def table_pass_cap(B: int, ns: int = 3) -> int:
+    """Passes the kernel's LDS table holds per block (fused_step.hip FD::TCAP)."""
+    return sum(-(-c // 64) + 2 for c in stage_face_counts(B, ns))
+
+
+def _pack_runs(runs: List[Tuple[int, int, List[int]]]) -> List[Tuple[int, int, int, int]]:
+    """Slots (ax, k, p, kind) of the shared passes: every run on consecutive
+    lanes, then the slope-only lane of its last upper cell.  A run that
+    crosses a pass boundary ends the pass with the slope-only copy of the
+    next pass's first face; no piece is shorter than FT_MIN_RUN."""
+    slots: List[Tuple[int, int, int, int]] = []
+    idle = (0, 0, 0, FT_IDLE)
+    for ax, p, ks in runs:
+        ks = list(ks)
+        while ks:
+            rem = 64 - len(slots) % 64
+            if len(ks) + 1 <= rem:
+                take = len(ks)
+            else:
+                take = min(rem - 1, len(ks) - FT_MIN_RUN)
+                if take < FT_MIN_RUN:
+                    slots += [idle] * rem
+                    continue
+            slots += [(ax, k, p, FT_SHARED) for k in ks[:take]]
+            slots.append((ax, ks[take - 1] + 1, p, FT_SLOPE))
+            ks = ks[take:]
+    slots += [idle] * (-len(slots) % 64)
+    return slots
+
+
+def face_table(B: int, cls: Tuple[int, int], ns: int = 3, share: Optional[bool] = None):
+    """Per stage of block class ``cls``: (entries [64 npass] uint16, near mask,
+    shared mask).  The full passes first: the faces next to a panel-edge line,
+    line-major, and the far faces of runs shorter than FT_MIN_RUN behind them;
+    then the shared passes (runs of far faces, row by row)."""
+    share = share_enabled() if share is None else share
+    d = FusedDims.make(B, ns)
+    lines = class_edge_lines(B, cls, ns)
+    out = []
+    for ax, k, p in stage_face_coords(B, ns):
+        near = np.zeros(len(k), bool)
+        for a_ in range(2):
+            for e in lines[a_]:
+                near |= (ax == a_) & (np.abs(k - e) <= 1)
+        if not share:
+            full = list(range(len(k)))
+            slots = []
+        else:
+            rows: Dict[Tuple[int, int], List[int]] = {}
+            for t in np.flatnonzero(~near):
+                rows.setdefault((int(ax[t]), int(p[t])), []).append(int(k[t]))
+            runs, short = [], set()
+            for (a_, p_), ks in sorted(rows.items()):
+                ks.sort()
+                cut = [0] + [i for i in range(1, len(ks)) if ks[i] != ks[i - 1] + 1] + [len(ks)]
+                for i0, i1 in zip(cut[:-1], cut[1:]):
+                    if i1 - i0 >= FT_MIN_RUN:
+                        runs.append((a_, p_, ks[i0:i1]))
+                    else:
+                        short.update((a_, k_, p_) for k_ in ks[i0:i1])
+            slots = _pack_runs(runs)
+            idx = np.arange(len(k))
+            full = list(idx[near]) + [t for t in idx[~near] if (int(ax[t]), int(k[t]), int(p[t])) in short]
+        # the full passes first: a pass next to a panel-edge line is the longest
+        # (codes, ghost wait), so it is scheduled first and is its wave's first
+        fslots = [(int(ax[t]), int(k[t]), int(p[t]), FT_FULL) for t in full]
+        fslots += [(0, 0, 0, FT_IDLE)] * (-len(fslots) % 64)
+        nfull = len(fslots) // 64
+        slots = fslots + slots
+        sa, sk, sp, kind = (np.array(x, np.int64) for x in zip(*slots))
+        idle = kind == FT_IDLE
+        sk[idle], sp[idle] = d.L1 + 1, d.L1            # idle lanes read window cells like any other
+        ent = ft_pack(sa, np.where(sa == 1, sp, sk), np.where(sa == 1, sk, sp), kind)
+        npass = len(slots) // 64
+        assert npass <= PASS_SLOTS
+        nearset = set(zip(ax[near].tolist(), k[near].tolist(), p[near].tolist()))
+        nm = 0
+        for q in range(nfull):
+            if any(s_[3] == FT_FULL and s_[:3] in nearset for s_ in slots[64 * q:64 * q + 64]):
+                nm |= 1 << q
+        out.append((ent, nm, ((1 << npass) - 1) & ~((1 << nfull) - 1)))
+    return out
+
+
+def pass_loads(tabs, weights: str) -> List[List[int]]:
+    """Load of every pass of ``face_table``'s stages in quarter passes, for the
+    greedy balance: a full pass 4 as in ``pass_schedule``; ``weights`` fields 3
+    and 4 ("corner:ghost:shared:near") give a shared pass (fewer instructions
+    per face) and a pass next to a panel-edge line (codes, ghost wait)."""
+    f = weights.split(":")
+    wsh, wnear = (int(f[2]), int(f[3])) if len(f) >= 4 else SHARE_LOADS
+    return [[wnear if (nm >> q) & 1 else wsh if (sm >> q) & 1 else 4 for q in range(len(ent) // 64)]
+            for ent, nm, sm in tabs]
+
+
+def face_tables(B: int, flags: np.ndarray, ncorner: np.ndarray, edge: np.ndarray, G: int, ns: int = 3,
+                share: Optional[bool] = None, weights: Optional[str] = None):
+    """The kernel's face tables of a plan: (ftab [classes, 64 cap] uint16,
+    sched [nb, ns, SCHED_WORDS] uint32, classes).  sched: per wave (16 words)
+    bit q = the wave runs pass q of the stage, balanced like ``pass_schedule``
+    over the class's pass counts; word 16 the near passes, word 17 the shared
+    passes, word 18 the stage's first pass in the class table, word 19 the
+    class's row of ftab."""
+    weights = weights or os.environ.get("STSP_FUSED_SCHED", "5:1")
+    nw = fused_threads(B, ns) // 64
+    cap = table_pass_cap(B, ns)
+    ngw = -(-G // 64) if G > 0 else 0
+    nb = len(flags)
+    classes = sorted(set(block_class(f) for f in flags))
+    ftab = np.zeros((len(classes), 64 * cap), dtype=np.uint16)
+    per_class = {}
+    for ci, cls in enumerate(classes):
+        tabs = face_table(B, cls, ns, share)
+        off = 0
+        offs = []
+        for ent, _, _ in tabs:
+            offs.append(off)
+            ftab[ci, 64 * off:64 * off + len(ent)] = ent
+            off += len(ent) // 64
+        if off > cap:
+            raise RuntimeError(f"fused step: {off} face passes of block class {cls} exceed the kernel's table ({cap})")
+        per_class[cls] = (ci, tabs, offs)
+    sched = np.zeros((nb, ns, SCHED_WORDS), dtype=np.uint32)
+    cache = {}
+    for b in range(nb):
+        cls = block_class(flags[b])
+        key = (cls, 1 if ncorner[b] > 0 else 0, ngw if edge[b] else 0)
+        if key not in cache:
+            ci, tabs, offs = per_class[cls]
+            wave = _balance_passes([len(t[0]) // 64 for t in tabs], nw, key[1], key[2], weights,
+                                   pass_loads(tabs, weights) if weights != "legacy" else None)
+            m = np.zeros((ns, SCHED_WORDS), dtype=np.uint32)
+            for s_, (ent, nm, sm) in enumerate(tabs):
+                for q in range(len(ent) // 64):
+                    m[s_, wave[s_, q]] |= np.uint32(1 << q)
+                m[s_, 16], m[s_, 17], m[s_, 18], m[s_, 19] = nm, sm, offs[s_], ci
+            cache[key] = m
+        sched[b] = cache[key]
+    return ftab, sched, classes
 
 
 def fused_supported(engine, B: Optional[int] = None) -> Optional[str]:
@@ -1269,11 +1469,28 @@ class FusedKernel:
             self.tens["pidx"] = torch.as_tensor(cell_producer_index(P, prod), device=dev).contiguous()
         # face passes per wave, balanced over the SIMDs (pass_schedule)
         edge_b = np.array([any(int(x) > 0 for x in np.unique(P.reg[b])) for b in range(nb)])
-        sched = pass_schedule(B, np.asarray(P.ccnt), edge_b, G)
-        assert int(sched.max()) < fused_threads(B) // 64
         flg = (org[:, 3].view(np.uint32) >> 24) & 0x1F
-        near = near_pass_masks(B, P.org, flg.astype(np.int64), e.layout.N)
-        self.tens["sched"] = torch.as_tensor(pass_masks(B, sched, near=near).view(np.int32), device=dev).contiguous()
+        self.pfn = fused_pfn(B, e.dtype == torch.float32)
+        if self.pfn:
+            # table-driven face passes: per-class tables, the schedule over their pass counts
+            R_ = d.R
+            for b in range(nb):     # a class's edge lines are the block's own sides
+                X0, Y0 = int(P.org[b, 0]), int(P.org[b, 1])
+                kx = [k for f_, k in ((2, -X0), (4, e.layout.N - X0)) if flg[b] & f_]
+                ky = [k for f_, k in ((8, -Y0), (16, e.layout.N - Y0)) if flg[b] & f_]
+                assert (kx, ky) == tuple(class_edge_lines(B, block_class(flg[b]))), (b, kx, ky, R_)
+            ftab, sched20, self.classes = face_tables(B, flg.astype(np.int64), np.asarray(P.ccnt), edge_b, G)
+            assert ftab.shape[1] == 64 * int(self.lib.stsp_fused_table_passes(B))
+        else:
+            sched = pass_schedule(B, np.asarray(P.ccnt), edge_b, G)
+            assert int(sched.max()) < fused_threads(B) // 64
+            near = near_pass_masks(B, P.org, flg.astype(np.int64), e.layout.N)
+            sched20 = np.zeros((nb, 3, SCHED_WORDS), dtype=np.uint32)
+            sched20[:, :, :17] = pass_masks(B, sched, near=near)
+            ftab = np.zeros((1, 64), dtype=np.uint16)
+        assert int(np.log2(np.maximum(sched20[:, :, :16].max(), 1))) < PASS_SLOTS
+        self.tens["sched"] = torch.as_tensor(sched20.view(np.int32), device=dev).contiguous()
+        self.tens["ftab"] = torch.as_tensor(ftab.view(np.int16), device=dev).contiguous()
         # per-face normals of the panel-edge blocks (the kernel's PFN builds)
         self.tens["nrmf"] = t(face_normals(P, flg.astype(np.int64)))
         self.timeout_ticks = int(timeout_s * 1e8)
@@ -1346,6 +1563,7 @@ class FusedKernel:
         d.PM = int(tn["prod"].shape[1])
         d.sched = p(tn["sched"])
         d.nrmf = p(tn["nrmf"])
+        d.ftab = p(tn["ftab"])
         d.hx = p(tn["hx"]) if self.handoff == "tag" else 0
         d.pidx = p(tn["pidx"]) if self.poll == "cell" else 0
         if self.mem is not None:

@@ -71,7 +71,7 @@ class FusedDesc(ctypes.Structure):
         ("local_src", ctypes.c_int), ("links", ctypes.c_int * 6),
         ("nsteps", ctypes.c_int), ("prod", ctypes.c_void_p), ("PM", ctypes.c_int),
         ("cpush", ctypes.c_void_p), ("sched", ctypes.c_void_p), ("nrmf", ctypes.c_void_p),
-        ("hx", ctypes.c_void_p), ("pidx", ctypes.c_void_p),
+        ("hx", ctypes.c_void_p), ("pidx", ctypes.c_void_p), ("ftab", ctypes.c_void_p),
     ]
 
 
@@ -196,6 +196,8 @@ def load(build_if_missing: bool = True):
         L.stsp_fused_limits.restype = ci
         L.stsp_fused_tagh.argtypes = []
         L.stsp_fused_tagh.restype = ci
+        L.stsp_fused_table_passes.argtypes = [ci]
+        L.stsp_fused_table_passes.restype = ci
         L.stsp_fused_record_words.argtypes = [ci]
         L.stsp_fused_record_words.restype = ci
         L.stsp_fused_prime_launch.argtypes = [ci, vp, ci, vp, vp, ci, vp, ci, ci, vp]
