@@ -88,6 +88,10 @@ def make_physics(pc) -> Any:
         raise ValueError(f"physics.operator: one of {list(OPERATORS)} expected, not {op!r}")
     if op == "consistent" and model != "diffusion":
         raise ValueError(f"physics.operator: consistent is defined for the diffusion model, not {model!r}")
+    flow, period_days = getattr(pc, "flow", None), getattr(pc, "period_days", None)
+    if (flow is not None or period_days is not None) and model != "advection":
+        raise ValueError(f"physics.flow / physics.period_days: the prescribed wind of the advection model, "
+                         f"not of {model!r}")
     layers = layers_spec(pc)
     if layers is not None:
         if tracers:
@@ -99,7 +103,15 @@ def make_physics(pc) -> Any:
             return ShallowWaterTracers(case, tracers=list(tracers), limiter=lim, alpha=pc.alpha, tracer_limiter=tlim)
         return ShallowWater(case, limiter=lim, alpha=pc.alpha)
     if model == "advection":
-        return Advection(case, alpha=pc.alpha, limiter=lim)
+        kw = {}
+        if flow is not None:
+            kw["flow"] = flow
+        if period_days is not None:
+            try:                                 # YAML 1.1 reads 1.2e1 (no sign in the exponent) as a string
+                kw["period"] = float(period_days) * DAY
+            except (TypeError, ValueError):
+                raise ValueError(f"physics.period_days: a number expected, not {period_days!r}") from None
+        return Advection(case, alpha=pc.alpha, limiter=lim, **kw)
     if model == "diffusion":
         try:                                     # YAML 1.1 reads 2.0e6 (no sign in the exponent) as a string
             kappa = float(pc.kappa)
@@ -278,6 +290,7 @@ class Solver(SolverDiagnostics):
         self.world, self.rank = 1, 0
         self._dspec = None            # physics.dissipation, checked (initialize)
         self._dinterval = 0           # model steps between its applications (doubles when dt is halved)
+        self._gstepper = None         # engine.GraphStepper of a time-dependent physics (one GPU, runtime.graph)
 
     # ---- setup ------------------------------------------------------------
     def setup_sharding(self) -> None:
@@ -302,6 +315,10 @@ class Solver(SolverDiagnostics):
         if self._dspec is not None and self.world > 1:
             raise ValueError("physics.dissipation: one process per rank (spmd) is not supported; run one "
                              "rank or virtual ranks in one process")
+        if (c.physics.flow or "solid_body") != "solid_body" and self.world > 1:
+            raise ValueError("physics.flow: a time-dependent wind with one process per rank (spmd) is not "
+                             "supported (the native runtime's graphs hold one set of transport tables and no step "
+                             "clock); run one rank or virtual ranks in one process")
         if c.physics.operator == "consistent" and self.world > 1:
             raise ValueError("physics.operator: consistent: one process per rank (spmd) is not supported; run one "
                              "rank or virtual ranks in one process")
@@ -349,6 +366,16 @@ class Solver(SolverDiagnostics):
         self.layout = TileLayout(N, t, nd, ng=max(c.grid.halo, phys0.halo), owner=self.sharding.owner)
         self.grid = self._geometry_stage(N, c.grid.radius or EARTH_RADIUS)
         dt = c.time.dt or (phys0.max_dt(self.grid, c.time.cfl) if c.time.cfl else phys0.max_dt(self.grid))
+        if phys0.time_dependent:
+            from .ops.hip_compute import MARCH_SHAPES
+            if c.runtime.block and tuple(c.runtime.block) in MARCH_SHAPES:
+                raise ValueError(f"physics.flow: runtime.block = {list(c.runtime.block)} is a march block of the "
+                                 f"streaming stage, which runs shallow water and reads no transport tables; a "
+                                 f"time-dependent wind steps through the block stage kernel")
+            if not c.time.dt:
+                # a whole number of steps per period: the run ends on t = m T, where the
+                # initial condition is the exact solution
+                dt = phys0.period / math.ceil(phys0.period / dt - 1e-9)
         kw = dict(grid=self.grid, dtype=dtype, device=device, backend=backend, integrator=c.time.integrator, dt=dt)
         if c.runtime.block:
             kw["block"] = tuple(c.runtime.block)
@@ -521,7 +548,8 @@ class Solver(SolverDiagnostics):
         h = self.global_field(0)
         if exact is None or h is None:
             return None
-        ht = exact(self.grid, self.time)
+        # a time-dependent wind returns the field at t = m T: the step decides what "at" means
+        ht = exact(self.grid, self.time, self.dt) if self.physics.time_dependent else exact(self.grid, self.time)
         if ht is None:
             return None
         return williamson_norms(h, ht, self.grid.areas())
@@ -557,6 +585,8 @@ class Solver(SolverDiagnostics):
             return False
         if getattr(self.physics, "two_pass", False):
             return False                 # two launches and an exchange per stage: eager, through Engine.step
+        if self.physics.time_dependent:
+            return False                 # a table launch per stage and a device clock: Engine.step / GraphStepper
         if self.mode == "single":
             return c.graph
         return self.mode == "spmd" and self.comm in ("xgmi", "rccl", "ipc")
@@ -742,8 +772,22 @@ class Solver(SolverDiagnostics):
             if self.runner is None:
                 self.runner = self._make_runner()
             self.runner.run(nsteps)
+        elif self._graph_stepper() is not None:
+            self._graph_stepper().run(nsteps)
         else:
             self.engines[0].step(nsteps)
+
+    def _graph_stepper(self):
+        """``engine.GraphStepper`` of a time-dependent physics on one GPU with
+        ``runtime.graph`` (built on first use), else None: eager steps."""
+        c = self.cfg.runtime
+        if not (self.physics.time_dependent and self.mode == "single" and self.backend == "hip" and c.graph
+                and not c.canary and self.device.type == "cuda"):
+            return None
+        if self._gstepper is None:
+            from .engine import GraphStepper
+            self._gstepper = GraphStepper(self.engines[0], steps_per_graph=c.steps_per_graph)
+        return self._gstepper
 
     def _sync(self) -> None:
         if self.device.type == "cuda":
@@ -878,6 +922,8 @@ class Solver(SolverDiagnostics):
                 self.runner.graph_periods = max(1, min(max(lens), 512) // per)
                 for k in lens[:8]:
                     self.runner.prepare(k)      # chunks shorter than a period: their remainder launch
+            if nsteps > 0:
+                self._graph_stepper()            # a time-dependent physics: warm-up and capture, before the clock starts
             if dissipation:
                 self._dissipations()             # tables and buffers, before the clock starts
             if deferred and ("watchdog" in iv or "metrics" in iv):
@@ -971,13 +1017,22 @@ class Solver(SolverDiagnostics):
                    "cell_updates_per_s": cells * done / max(wall, 1e-12),
                    "sim_days_per_day": ((self.time - t0) / DAY) / max(wall / DAY, 1e-30),
                    "recoveries": recoveries, "dt_final": self.dt,
-                   "graph_steps": (self.runner.stats["graph_steps"] if self.runner is not None else 0),
+                   "graph_steps": (self.runner.stats["graph_steps"] if self.runner is not None else
+                                   self._gstepper.graph_steps if self._gstepper is not None else 0),
                    "runtime": ("fused" if getattr(self, "fused", None) is not None else
-                               "native" if self.runner is not None else "eager"),
+                               "native" if self.runner is not None else
+                               "graph" if self._gstepper is not None else "eager"),
                    "fused_direct_steps": (self.runner.stats["direct_steps"] if self.runner is not None else 0),
                    "kernel_launches": (self.runner.stats["launches"] if self.runner is not None else 0),
                    "phase_s": dict(ph.times)}
         summary.update(self.diagnostics())
+        if self.physics.time_dependent:      # the deformational-flow tests: extrema and the mass against the start
+            q = self.global_field(0)
+            if q is not None:
+                area = self.grid.areas()
+                m0 = float((self.physics.initial_global(self.grid) * area).sum())
+                summary.update(q_min=float(q.min()), q_max=float(q.max()),
+                               mass_drift=float(((q * area).sum() - m0) / m0))
         norms = self.error_norms()
         if norms is not None:
             summary.update({f"err_{k}": v for k, v in norms.items()})
@@ -987,6 +1042,10 @@ class Solver(SolverDiagnostics):
                 summary.update({f"tracer{j}_err_{k}": v for k, v in tn.items()})
         self._log(f"Run complete: {done} steps, {summary['sim_days']:.3f} days, "
                   f"{summary['cell_updates_per_s']:.3e} cell-updates/s (setup {summary['setup_s']:.3f} s excluded)")
+        if self.physics.time_dependent and "err_l2" in summary:
+            self._log(f"Error norms at t = {self.time / self.physics.period:.3f} T: l1 {summary['err_l1']:.4e}, "
+                      f"l2 {summary['err_l2']:.4e}, linf {summary['err_linf']:.4e}; q in [{summary['q_min']:.4f}, "
+                      f"{summary['q_max']:.4f}], relative mass drift {summary['mass_drift']:.2e}")
         return summary
 
     # ---- run-loop helpers ----------------------------------------------------------
@@ -1127,6 +1186,7 @@ class Solver(SolverDiagnostics):
         self.dt = dt
         for e in self.engines:
             e.dt = dt
+        self._gstepper = None        # its graph bakes dt in
         if self.runner is not None:
             self.runner.set_dt(dt)   # graphs bake dt in: the runner re-records
 

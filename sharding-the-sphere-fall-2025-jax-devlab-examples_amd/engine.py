@@ -16,6 +16,15 @@ A physics with ``two_pass`` (the consistent diffusion) steps through
 ``ops.heat.ConsistentCompute`` on either backend: its stages have a middle phase
 (``stage_mid``: finish the exchange of Q, first pass, start the exchange of its
 scratch) between ``stage_begin`` and ``stage_end``, and an ``end_step`` hook.
+
+A physics with ``time_dependent`` (the deformational winds of
+models/advection.py) has its tables refreshed at the top of every stage, at the
+stage time t_s = (step_count + c_s) dt.  With ``backend='torch'`` the host
+evaluates them (``Physics.update``); with ``backend='hip'`` one launch of
+``ops/csrc/wind_kernel.hip`` does, and the step count it reads lives on the
+device (``ops/wind.py``): a tick launch in ``end_step`` advances it, so a
+captured graph of k steps sees k different times on every replay.  Assigning
+``Engine.step_count`` writes the device's copy too.
 """
 from __future__ import annotations
 
@@ -90,6 +99,8 @@ class Engine:
         self.halo_src = torch.as_tensor(self.plan.halo_src, dtype=torch.long, device=self.device)
         self.halo_dst = torch.as_tensor(self.plan.halo_dst, dtype=torch.long, device=self.device)
         self.transport = transport or NullTransport(self.plan, F, dtype, self.device)
+        self.clock = None           # ops.wind.WindCompute: the device's step count and the table launch
+        self._step_count = 0
         self.set_state(torch.as_tensor(physics.initial_state(self.geo), dtype=dtype))
         self.dt = float(dt) if dt is not None else (physics.max_dt(self.grid) if cfl is None else physics.max_dt(self.grid, cfl))
         self.time = 0.0
@@ -110,6 +121,45 @@ class Engine:
         else:
             from .ops.hip_compute import HipCompute
             self.compute = HipCompute(self)
+        if getattr(physics, "time_dependent", False) and backend == "hip":
+            if getattr(physics, "two_pass", False):
+                raise ValueError(f"{physics.name}: a time-dependent physics with two passes per stage is not supported")
+            from .ops.wind import WindCompute
+            self.clock = WindCompute(self)
+            self.clock.set(self._step_count)
+
+    # ---- clock ------------------------------------------------------------
+    @property
+    def step_count(self) -> int:
+        return self._step_count
+
+    @step_count.setter
+    def step_count(self, k: int) -> None:
+        """The host's step count, and the device's with it: every assignment
+        from outside a step (construction, a restored checkpoint, the count put
+        back after a graph capture, whose warm-up steps ran and whose captured
+        ticks did not) is a point where the two could disagree."""
+        self._step_count = int(k)
+        if self.clock is not None:
+            self.clock.set(self._step_count)
+
+    def replayed(self, k: int) -> None:
+        """k steps were run by a graph replay: their captured ticks have advanced
+        the device's count already, so only the host's moves (no launch)."""
+        self._step_count += int(k)
+
+    def stage_time(self, st: Stage) -> float:
+        """t_s = (step_count + c_s) dt, from the integer step count."""
+        return (self._step_count + st.t) * self.dt
+
+    def update_physics(self, st: Stage) -> None:
+        """Refresh the time-dependent tables for stage ``st`` (nothing for a steady physics)."""
+        if not getattr(self.physics, "time_dependent", False):
+            return
+        if self.clock is not None:
+            self.clock.update(st.t, self.dt)
+        else:
+            self.physics.update(self.geo, self.tens, self.stage_time(st))
 
     # ---- state ------------------------------------------------------------
     @property
@@ -124,6 +174,8 @@ class Engine:
         """q: [F, T, n, n] interior values (any device); refreshes the halos."""
         self.interior(self.pool[0]).copy_(q.reshape(self.physics.F, self.plan.T, self.plan.n, self.plan.n))
         self.refresh_halos(self.pool[0])
+        if self.clock is not None:
+            self.clock.set(self._step_count)
 
     def refresh_halos(self, q: torch.Tensor) -> None:
         """Fill the same-rank ghost slots of a padded buffer from their source
@@ -179,6 +231,7 @@ class Engine:
             self.pool[st.out][:, self.halo_dst] = float("nan")
             if self.transport.recv.numel():
                 self.transport.recv.fill_(float("nan"))
+        self.update_physics(st)
         self.transport.start(self.pool[st.Q])
         self.compute.stage(st, self.dt, None, part="interior")
 
@@ -206,7 +259,9 @@ class Engine:
         rot = self.integ.rotation
         self.pool = [self.pool[r] for r in rot]
         self.time += self.dt
-        self.step_count += 1
+        self._step_count += 1
+        if self.clock is not None:
+            self.clock.tick()        # the device's count, by a launch: it replays with a captured step
         fin = getattr(self.compute, "end_step", None)
         if fin is not None:
             fin()
@@ -350,8 +405,11 @@ class GraphStepper:
         with torch.cuda.graph(self.graph, stream=self.stream):
             engine.step(self.k)
         engine.pool = pool0
+        # the warm-up steps ticked the device's step count and the captured ones did
+        # not: this assignment puts c0 back on both sides (Engine.step_count)
         engine.time, engine.step_count = t0, c0
         self._pool0 = list(pool0)
+        self.graph_steps = 0        # steps run by replays so far
 
     def _sync_pool(self) -> None:
         """The graph holds the construction-order buffer pointers; after an
@@ -371,8 +429,13 @@ class GraphStepper:
         full, rem = divmod(nsteps, self.k)
         for _ in range(full):
             self.graph.replay()
+        self.graph_steps += full * self.k
         e.time += full * self.k * e.dt
-        e.step_count += full * self.k
+        done = getattr(e, "replayed", None)     # an Engine: the replayed ticks moved the device's count
+        if done is not None:
+            done(full * self.k)
+        else:                                   # an engine-like core (the batched ensemble)
+            e.step_count += full * self.k
         if rem:
             e.step(rem)
             self._sync_pool()

@@ -128,12 +128,16 @@ class Ensemble:
         self.steps_per_graph = steps_per_graph
         self._graph = None
         self._stats = None
-        phys0 = None
+        phys0 = physics_factory()
+        if getattr(phys0, "time_dependent", False):
+            raise ValueError(f"an ensemble of a time-dependent physics ({phys0.name}, flow "
+                             f"{getattr(phys0, 'flow', None)!r}) is not supported in mode {mode!r}: the members' "
+                             f"graphs and the batched stage hold one set of tables and no step clock; step the "
+                             f"members as separate engines")
         engine_kw = {}
         if block is not None:
             engine_kw["block"] = tuple(block)
         if mode == "batched":
-            phys0 = physics_factory()
             block = self._batched_block(phys0, layout, members, dtype, torch.device(device), backend, block)
             if block is not None:
                 engine_kw["block"] = block

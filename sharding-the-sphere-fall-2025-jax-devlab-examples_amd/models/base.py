@@ -478,6 +478,12 @@ class Physics:
     kernel_id = -1
     fields: List[str] = []
     halo = 2
+    # the rhs depends on time through tables of ``tens``: the engine calls ``update``
+    # before every stage with the stage time (step_count + c_s) dt
+    time_dependent = False
+
+    def update(self, geo: "RankGeometry", tens: Dict[str, torch.Tensor], t: float) -> None:
+        """Refresh, in place, the tables of ``tens`` that depend on time."""
 
     @property
     def F(self) -> int:

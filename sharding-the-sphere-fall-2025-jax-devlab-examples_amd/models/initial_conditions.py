@@ -18,6 +18,10 @@ invariant representation the reference exchanges across cube edges (PDF s.18
                         ``constant``, ``cosine_bell``, ``cap``, ``gradient``.
 * ``layered_fields``    two-layer (stacked shallow water) states: ``tc2``, ``rest``,
                         ``tc5``, ``layered_jet``, ``layered_jet_balanced``.
+* ``deform_wind``       time-dependent deformational flows (Nair & Lauritzen 2010,
+                        Lauritzen et al. 2012) with ``deform_streamfunction`` and the
+                        cases of ``deform_tracer``: ``cosine_bells``,
+                        ``gaussian_hills``, ``slotted_cylinders``.
 * ``lima_flag``         checkerboard heat source on the top panel (face 0) on a
                         1 K background (PDF s.12 / s.17, log scale 1..1000 K).
 """
@@ -339,3 +343,90 @@ def layered_fields(case, p, depths=None, density_ratio=0.9, winds=None, jet_scal
                              f"(minimum {h[k].min():.6g} m) with depths {[H0, H1]}, density_ratio {r}; "
                              f"use deeper layers, weaker winds or a smaller density_ratio")
     return h, wind, b
+
+
+# ----------------------------------------------------------------------------
+# Deformational flows (Nair & Lauritzen 2010; Lauritzen et al. 2012): prescribed
+# winds that depend on time, reverse at t = T / 2 and return the tracer to its
+# initial condition at t = T.
+# ----------------------------------------------------------------------------
+
+DEFORM_FLOWS = ("deform_nd", "deform_nd_static", "deform_div")
+STREAM_FLOWS = ("deform_nd", "deform_nd_static")
+DEFORM_CASES = ("cosine_bells", "gaussian_hills", "slotted_cylinders")
+DEFORM_CENTERS = ((5.0 * math.pi / 6.0, 0.0), (7.0 * math.pi / 6.0, 0.0))
+
+
+def deform_amplitude(flow: str, radius: float, period: float) -> float:
+    """k of the flow: 10 R / T for the non-divergent flows, 5 R / T for the divergent one."""
+    if flow not in DEFORM_FLOWS:
+        raise ValueError(f"unknown deformational flow {flow!r}; choose from {list(DEFORM_FLOWS)}")
+    return (5.0 if flow == "deform_div" else 10.0) * radius / period
+
+
+def deform_rotation(flow: str, radius: float, period: float) -> float:
+    """Speed 2 pi R / T of the background rotation (0 for ``deform_nd_static``)."""
+    return 0.0 if flow == "deform_nd_static" else 2.0 * math.pi * radius / period
+
+
+def deform_streamfunction(lon, lat, t: float, flow: str = "deform_nd", radius=EARTH_RADIUS, period=12.0 * DAY):
+    """psi (m^2/s) of the non-divergent flows, v = k_hat x grad psi:
+    psi = R [k sin^2(lam') cos^2(th) cos(pi t / T) - u_rot sin(th)],
+    lam' = lam - 2 pi t / T with the background rotation u_rot = 2 pi R / T
+    (``deform_nd``, NL2010 case 4), lam' = lam without (``deform_nd_static``, case 2)."""
+    if flow not in STREAM_FLOWS:
+        raise ValueError(f"{flow!r} has no streamfunction; choose from {list(STREAM_FLOWS)}")
+    k = deform_amplitude(flow, radius, period)
+    urot = deform_rotation(flow, radius, period)
+    lp = lon - 2.0 * math.pi * t / period if urot else lon
+    return radius * (k * np.sin(lp) ** 2 * np.cos(lat) ** 2 * math.cos(math.pi * t / period) - urot * np.sin(lat))
+
+
+def deform_wind_uv(lon, lat, t: float, flow: str = "deform_nd", radius=EARTH_RADIUS, period=12.0 * DAY):
+    """(u, v) zonal / meridional wind (m/s) of a deformational flow at time t."""
+    k = deform_amplitude(flow, radius, period)
+    urot = deform_rotation(flow, radius, period)
+    lp = lon - 2.0 * math.pi * t / period if urot else lon
+    c = math.cos(math.pi * t / period)
+    if flow == "deform_div":
+        u = -k * np.sin(0.5 * lp) ** 2 * np.sin(2.0 * lat) * np.cos(lat) ** 2 * c + urot * np.cos(lat)
+        v = 0.5 * k * np.sin(lp) * np.cos(lat) ** 3 * c
+    else:
+        u = k * np.sin(lp) ** 2 * np.sin(2.0 * lat) * c + urot * np.cos(lat)
+        v = k * np.sin(2.0 * lp) * np.cos(lat) * c
+    return u, v
+
+
+def deform_wind(p, t: float, flow: str = "deform_nd", radius=EARTH_RADIUS, period=12.0 * DAY):
+    """Cartesian wind of a deformational flow at unit positions p [..., 3]."""
+    lon, lat = xyz_to_lonlat(p)
+    u, v = deform_wind_uv(lon, lat, t, flow, radius, period)
+    e, n = lonlat_vectors(p)
+    return u[..., None] * e + v[..., None] * n
+
+
+def deform_tracer(p, case: str):
+    """Initial mixing ratio of the deformational-flow tests at unit positions
+    p [..., 3]: two ``cosine_bells`` (background 0.1, peak 1), ``gaussian_hills``
+    (peak 0.95) or ``slotted_cylinders`` (0.1 / 1) centred at ``DEFORM_CENTERS``."""
+    lon, lat = xyz_to_lonlat(p)
+    r = [great_circle_distance(lon, lat, lc, tc, 1.0) for lc, tc in DEFORM_CENTERS]
+    if case == "cosine_bells":
+        q = np.full(lon.shape, 0.1)
+        for ri in r:
+            q = np.where(ri < 0.5, 0.1 + 0.9 * 0.5 * (1.0 + np.cos(math.pi * ri / 0.5)), q)
+        return q
+    if case == "gaussian_hills":
+        q = np.zeros(lon.shape)
+        for lc, tc in DEFORM_CENTERS:
+            x = np.array([math.cos(tc) * math.cos(lc), math.cos(tc) * math.sin(lc), math.sin(tc)])
+            q = q + 0.95 * np.exp(-5.0 * np.sum((p - x) ** 2, axis=-1))
+        return q
+    if case == "slotted_cylinders":
+        (l1, t1), (l2, t2) = DEFORM_CENTERS
+        d1, d2 = np.abs(lon - l1), np.abs(lon - l2)
+        inside = ((r[0] <= 0.5) & (d1 >= 1.0 / 12.0)) | ((r[1] <= 0.5) & (d2 >= 1.0 / 12.0))
+        inside |= (r[0] <= 0.5) & (d1 < 1.0 / 12.0) & (lat - t1 < -5.0 / 24.0)
+        inside |= (r[1] <= 0.5) & (d2 < 1.0 / 12.0) & (lat - t2 > 5.0 / 24.0)
+        return np.where(inside, 1.0, 0.1)
+    raise ValueError(f"unknown deformational-flow case {case!r}; choose from {list(DEFORM_CASES)}")

@@ -11,7 +11,10 @@ Every stage is one fused kernel launch (HIP path) computing
     acc_out = c0 * ACC + c1 * X + c2 * dt * L(Q)      (RK4 only)
 
 where Q is the stage input read *with halos* and X / ACC are read only at the
-cell being written.  Buffers are named by pool index; ``rotation`` maps the
+cell being written.  ``t`` is the stage's abscissa: a physics whose rhs depends
+on time (``Physics.time_dependent``) is evaluated at (step_count + t) * dt, from
+the integer step count, so that every execution path forms the same bits.
+Buffers are named by pool index; ``rotation`` maps the
 pool after a step (identity except for Euler, which ping-pongs), so a step is
 buffer-invariant after ``period`` steps and can be captured in one hipGraph.
 """
@@ -34,6 +37,7 @@ class Stage:
     c0: float = 0.0
     c1: float = 0.0
     c2: float = 0.0
+    t: float = 0.0      # abscissa c_s: the stage's rhs is evaluated at (step_count + t) * dt
 
 
 @dataclass(frozen=True)
@@ -61,24 +65,24 @@ def euler() -> Integrator:
 def ssp_rk2() -> Integrator:
     return Integrator("ssprk2", (
         Stage(0, 0, 1, 0.0, 1.0, 1.0),
-        Stage(0, 1, 0, 0.5, 0.5, 0.5),
+        Stage(0, 1, 0, 0.5, 0.5, 0.5, t=1.0),
     ), 2, (0, 1), 2)
 
 
 def ssp_rk3() -> Integrator:
     return Integrator("ssprk3", (
         Stage(0, 0, 1, 0.0, 1.0, 1.0),
-        Stage(0, 1, 2, 0.75, 0.25, 0.25),
-        Stage(0, 2, 0, 1.0 / 3.0, 2.0 / 3.0, 2.0 / 3.0),
+        Stage(0, 1, 2, 0.75, 0.25, 0.25, t=1.0),
+        Stage(0, 2, 0, 1.0 / 3.0, 2.0 / 3.0, 2.0 / 3.0, t=0.5),
     ), 3, (0, 1, 2), 3)
 
 
 def rk4() -> Integrator:
     return Integrator("rk4", (
         Stage(0, 0, 1, 0.0, 1.0, 0.5, acc_in=-1, acc_out=3, c0=0.0, c1=1.0, c2=1.0 / 6.0),
-        Stage(0, 1, 2, 1.0, 0.0, 0.5, acc_in=3, acc_out=3, c0=1.0, c1=0.0, c2=1.0 / 3.0),
-        Stage(0, 2, 1, 1.0, 0.0, 1.0, acc_in=3, acc_out=3, c0=1.0, c1=0.0, c2=1.0 / 3.0),
-        Stage(3, 1, 0, 1.0, 0.0, 1.0 / 6.0),
+        Stage(0, 1, 2, 1.0, 0.0, 0.5, acc_in=3, acc_out=3, c0=1.0, c1=0.0, c2=1.0 / 3.0, t=0.5),
+        Stage(0, 2, 1, 1.0, 0.0, 1.0, acc_in=3, acc_out=3, c0=1.0, c1=0.0, c2=1.0 / 3.0, t=0.5),
+        Stage(3, 1, 0, 1.0, 0.0, 1.0 / 6.0, t=1.0),
     ), 4, (0, 1, 2, 3), 4)
 
 

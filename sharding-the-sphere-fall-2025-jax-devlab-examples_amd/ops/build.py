@@ -18,7 +18,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libstsp.so")
-SOURCES = ["stage_kernel.hip", "march_kernel.hip", "march3_kernel.hip", "swe_tracer_stage.hip", "swe_layer_stage.hip", "fused_step.hip", "derived_kernel.hip", "dissipation_kernel.hip", "heat_kernel.hip", "ensemble_kernel.hip", "latlon_kernel.hip", "points_kernel.hip", "spectra_kernel.hip", "synth_kernel.hip", "tt_kernels.hip", "tt_persist.hip", "runtime.cpp"]
+SOURCES = ["stage_kernel.hip", "march_kernel.hip", "march3_kernel.hip", "swe_tracer_stage.hip", "swe_layer_stage.hip", "fused_step.hip", "derived_kernel.hip", "dissipation_kernel.hip", "heat_kernel.hip", "wind_kernel.hip", "ensemble_kernel.hip", "latlon_kernel.hip", "points_kernel.hip", "spectra_kernel.hip", "synth_kernel.hip", "tt_kernels.hip", "tt_persist.hip", "runtime.cpp"]
 HEADERS = ["stsp_kernels.h", "stage_common.h", "xg_ring.h", "xg_codec.h", "march_common.h", "tt_common.h", "runtime.h", "rccl_abi.h"]
 ARCH = os.environ.get("STSP_OFFLOAD_ARCH", "gfx950")
 # library variants: "" = production; "diag" = in-kernel phase stamps of the

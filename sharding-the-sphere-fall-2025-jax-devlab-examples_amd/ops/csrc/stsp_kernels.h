@@ -437,6 +437,29 @@ typedef struct EnsStatsDesc {
 } EnsStatsDesc;
 int stsp_ensemble_stats_launch(int dtype, const EnsStatsDesc* d, hipStream_t stream);
 int stsp_ensemble_stats_desc_size(void);
+// Time-dependent winds of the advection model (wind_kernel.hip, ops/wind.py; the
+// twin: models/advection.py): one launch before a Runge-Kutta stage refills the
+// stage kernel's transport tables ex / ey in place at the stage time
+// t_s = ((double)count[0] + cs) * dt.  The step count lives on the device and
+// stsp_wind_tick adds one to it.  Every table and all arithmetic is float64;
+// `dtype` is the element type of ex and ey.
+typedef struct WindDesc {
+  void* ex;             // [T][n][n+1] out (element type)
+  void* ey;             // [T][n+1][n] out (element type)
+  const double* vtab;   // mode 0: [4][T][n+1][n+1] vertex factors sin lam, cos lam, P, Q
+  const double* xtab;   // mode 1: [5][T][n][n+1] x-edge factors sin lam, cos lam, A, B, C
+  const double* ytab;   // mode 1: [5][T][n+1][n]
+  const int* count;     // [1] the step count
+  int ntile, n;
+  int nblocks;          // mode 0: ntile * ceil(n / 16)^2; mode 1: ceil(2 ntile n (n+1) / 256)
+  int mode;             // 0 streamfunction (vertex differences), 1 midpoint rule
+  double dt, cs;        // the step and the stage's abscissa
+  double omega;         // w of lam' = lam - w t (2 pi / T; 0 without the background rotation)
+  double pi_over_T;     // c(t) = cos(pi_over_T * t)
+} WindDesc;
+int stsp_wind_launch(int dtype, const WindDesc* d, hipStream_t stream);
+int stsp_wind_tick(int* count, hipStream_t stream);
+int stsp_wind_desc_size(void);
 // Direct xGMI halo build constant: ring slots.
 int stsp_xg_slots(void);
 }

@@ -230,6 +230,10 @@ class NativeStepper:
         e = engine
         if not isinstance(e.compute, HipCompute):
             raise RuntimeError("NativeStepper needs an Engine with backend='hip'")
+        if getattr(e.physics, "time_dependent", False):
+            raise ValueError(f"NativeStepper: {e.physics.name} with a time-dependent wind needs a table launch per "
+                             f"stage and the device's step clock, which the C++ op list does not carry; step through "
+                             f"Engine.step or engine.GraphStepper")
         self.e = e
         self.L = lib()
         hc = e.compute

@@ -51,6 +51,12 @@ class PhysicsConfig:
     case: Optional[str] = None    # tc2 | tc5 | tc6 | galewsky | galewsky_balanced | rest | cosine_bell | gaussian | lima_flag | harmonic | harmonic32
     limiter: str = "mc"
     alpha: float = 0.0
+    # advection only: the prescribed wind.  solid_body (steady) | deform_nd | deform_nd_static |
+    # deform_div: the deformational flows of Nair & Lauritzen (2010) / Lauritzen et al. (2012),
+    # which depend on time, reverse at period / 2 and return the tracer at `period_days`
+    # (cases cosine_bells | gaussian_hills | slotted_cylinders); null = solid_body, 12 days
+    flow: Optional[str] = None
+    period_days: Optional[float] = None
     kappa: float = 2.0e6
     # diffusion only: the Laplacian.  two_point: the flux kappa L / d across every edge
     # (conservative, monotone, not consistent: the error does not fall under
