@@ -70,7 +70,14 @@ class NullTransport(Transport):
 
 
 class TorchDistTransport(Transport):
-    """Grouped P2P over torch.distributed (gloo / RCCL)."""
+    """Grouped P2P over torch.distributed (gloo / RCCL).
+
+    gloo's send / recv take CPU tensors only (they hand the tensor's address to
+    a socket write).  With device buffers and a gloo group (ranks sharing one
+    GPU, STSP_SHARE_GPU=1) the messages are staged: pack on the device, copy to
+    a pinned host buffer, exchange the host buffers, copy into ``recv`` in
+    ``finish``; the rule of ``diagnostics.py::_sum_terms``.  A nccl group
+    exchanges the device buffers themselves."""
 
     def __init__(self, plan, F, dtype, device, group=None, staged: bool = False):
         super().__init__(plan, F, dtype, device)
@@ -78,24 +85,39 @@ class TorchDistTransport(Transport):
         self.staged = staged
         self._reqs = []
         self._stages = None
+        self.host_staged = None     # settled at the first start(): the group may not exist at construction
+        self._hsend = self._hrecv = None
         if staged:
             self._stages = device_stages(plan)
+
+    def _through_host(self) -> bool:
+        if self.host_staged is None:
+            import torch.distributed as dist
+            self.host_staged = self.recv.is_cuda and dist.get_backend(self.group) == "gloo"
+            if self.host_staged:
+                self._hsend = torch.empty((self.send_idx.numel(), self.F), dtype=self.dtype, pin_memory=True)
+                self._hrecv = torch.empty(tuple(self.recv.shape), dtype=self.dtype, pin_memory=True)
+        return self.host_staged
 
     def _ops(self, peers=None):
         import torch.distributed as dist
         ops = []
         p = self.plan
+        # only start() calls this, after _through_host() has settled host_staged (True or False)
+        send, recv = (self._hsend, self._hrecv) if self.host_staged else (self.send, self.recv)
         for peer, off, cnt in zip(p.send_peers, p.send_offsets, p.send_counts):
             if peers is None or peer in peers:
-                ops.append(dist.P2POp(dist.isend, self.send[off:off + cnt], peer, self.group))
+                ops.append(dist.P2POp(dist.isend, send[off:off + cnt], peer, self.group))
         for peer, off, cnt in zip(p.recv_peers, p.recv_offsets, p.recv_counts):
             if peers is None or peer in peers:
-                ops.append(dist.P2POp(dist.irecv, self.recv[off:off + cnt], peer, self.group))
+                ops.append(dist.P2POp(dist.irecv, recv[off:off + cnt], peer, self.group))
         return ops
 
     def start(self, q):
         import torch.distributed as dist
         self.send = self.pack_fn(q, self.send_idx)
+        if self._through_host():
+            self._hsend.copy_(self.send)          # blocking: the host buffer is complete when the sends are posted
         if self.staged:
             # stage by stage; each stage completes before the next (debug mode)
             for partners in self._stages:
@@ -104,6 +126,8 @@ class TorchDistTransport(Transport):
                     for r in dist.batch_isend_irecv(ops):
                         r.wait()
             self._reqs = []
+            if self.host_staged:
+                self.recv.copy_(self._hrecv)
             return
         ops = self._ops()
         self._reqs = dist.batch_isend_irecv(ops) if ops else []
@@ -111,6 +135,8 @@ class TorchDistTransport(Transport):
     def finish(self):
         for r in self._reqs:
             r.wait()
+        if self.host_staged and self._reqs:
+            self.recv.copy_(self._hrecv)
         self._reqs = []
         return self.recv
 

@@ -374,3 +374,21 @@ def test_latlon_and_spectra_frames_on_two_virtual_ranks(tmp_path):
     for name in ("pv1", "vorticity0", "eta1"):
         assert np.array_equal(s.derived_field(name), s1.derived_field(name)), name
     assert not np.array_equal(s1.derived_field("pv0"), s1.derived_field("pv1"))
+
+
+def test_spmd_gloo_ranks_state_restart_and_products(tmp_path):
+    """The Solver on two SPMD gloo ranks (receive rows of 8 values): state,
+    restart from the step-3 checkpoint, lat-lon fields, samples and the derived
+    fields of both layers (each layer's columns of the receive rows) equal the
+    one-rank run bit for bit, the spectra to 1e-12."""
+    from rank_products import assert_equal, reference, spmd_run
+
+    def cfg(out, nd):
+        c = _cfg(out, nd=nd, t=1, case="tc5")
+        c["physics"]["layers"] = {"depths": [2000.0, 5960.0], "density_ratio": 0.9}
+        return c
+    got = spmd_run(cfg(tmp_path / "ranks", 2), "layers", 2, tmp_path)
+    state, prods = reference(cfg(tmp_path / "one", 1), "layers", 6)
+    assert state.shape == (8, 6, 12, 12)
+    assert_equal(got, state, prods, "layers, 2 gloo ranks")
+    assert not np.array_equal(prods["latlon_h1"], prods["latlon_eta1"])      # tc5: b != 0 under the lower layer

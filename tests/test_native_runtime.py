@@ -3,6 +3,7 @@
 The loopback layout routes every ghost through pack -> RCCL grouped
 send/recv (to self) -> receive-buffer gather, i.e. the complete multi-GPU
 path, on a single MI355X."""
+import functools
 import os
 import socket
 
@@ -11,10 +12,14 @@ import torch
 
 from stsphere.engine import Engine
 from stsphere.models.geometry import CubedSphereGrid
-from stsphere.models.swe import ShallowWater
+from stsphere.models.swe import ShallowWater, ShallowWaterTracers
 from stsphere.models.advection import Advection
-from stsphere.parallel.comm import NativeBuffers
+from stsphere.parallel.comm import LoopbackTransport, NativeBuffers
 from stsphere.parallel.layout import TileLayout
+
+import layer_states
+import tracer_states
+from rough_states import grid_of, install
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +32,16 @@ def _single(N=24, t=2, phys=lambda: ShallowWater("tc5"), integ="ssprk3"):
 # the physics of the loopback transports: MC-limited (two ghost layers), and PPM
 # (limiter 4) with three layers and 3 x 3 carried corners in every message
 MK = {"swe": lambda: ShallowWater("tc5"), "adv": lambda: Advection(),
-      "swe_ppm": lambda: ShallowWater("tc5", limiter=4), "adv_ppm": lambda: Advection(limiter=4)}
+      "swe_ppm": lambda: ShallowWater("tc5", limiter=4), "adv_ppm": lambda: Advection(limiter=4),
+      # receive rows wider than 4 values: tracers behind (h, M) (F = 4 + NQ; PPM mixing
+      # ratios read three ghost layers), two layers (F = 8)
+      "trc1": lambda: _tracers(1), "trc3": lambda: _tracers(3), "trc4": lambda: _tracers(4),
+      "trc2_ppm": lambda: _tracers(2, tracer_limiter="ppm"), "layers": lambda: layer_states.layer_physics()}
+WIDE_F = {"trc1": 5, "trc3": 7, "trc4": 8, "trc2_ppm": 6, "layers": 8}
+
+
+def _tracers(nq, **kw):
+    return ShallowWaterTracers("tc5", tracers=tracer_states.TRACER_SETS[nq], limiter=2, **kw)
 
 
 @pytest.mark.parametrize("use_graph", [True, False])
@@ -167,7 +181,7 @@ def _ipc_loopback(use_graph, integ, phys):
     L = TileLayout(24, 2, 1, ng=mk().halo, loopback=True)
     p = L.plan(0)
     e = Engine(mk(), L, grid=g, device="cuda", backend="hip", dt=ref.dt, integrator=integ,
-               transport=NativeBuffers(p, 4, torch.float64, torch.device("cuda")))
+               transport=NativeBuffers(p, ref.physics.F, torch.float64, torch.device("cuda")))
     assert e.compute.remote and e.compute.blk_boundary.numel() > 0
     ipc = IpcExchange(e, IpcExchange.slots_for(e))
     ns = NativeStepper(e, use_graph=use_graph, steps_per_graph=3, ipc=ipc)
@@ -209,3 +223,119 @@ def test_ipc_copy_kernel_word_sizes(phys, dtype):
     assert torch.equal(ref.tiles_view(), e.tiles_view())
     ns.close()
     ipc.close()
+
+
+# ---- receive rows of 5 to 8 values: tracers and layers through the loopback transports ----------
+WIDE_N, WIDE_T, WIDE_STEPS = 24, 2, 6       # n = 12: partial blocks, tile sides on and inside panel edges, carried corners
+
+
+def _wide_engine(phys, dtype, block, dt=None, transport=None):
+    """An engine of MK[phys] on C24 t = 2 from the rough state of tracer_states.py
+    / layer_states.py (the cap and the bell are zero on most of the sphere; the
+    rough states put signal into every column of every receive row).
+    ``transport``: a transport class for the loopback layout, None for the plain
+    one-rank layout."""
+    ph = MK[phys]()
+    F = WIDE_F[phys]
+    assert ph.F == F
+    L = TileLayout(WIDE_N, WIDE_T, 1, ng=ph.halo, loopback=transport is not None)
+    tr = None if transport is None else transport(L.plan(0), F, dtype, torch.device("cuda"))
+    e = Engine(ph, L, grid=grid_of(WIDE_N), dtype=dtype, device="cuda", backend="hip", block=block, dt=dt, transport=tr)
+    assert (e.compute.bx, e.compute.by) == block and not e.compute.march
+    if transport is not None:
+        assert e.compute.remote and e.compute.blk_boundary.numel() > 0 and tuple(tr.recv.shape) == (L.plan(0).num_recv, F)
+    G = layer_states.global_state(WIDE_N, "rough") if phys == "layers" else tracer_states.global_state(F - 4, WIDE_N, "rough")
+    install(e, G)
+    return e
+
+
+@functools.lru_cache(maxsize=None)
+def _wide_reference(phys, dtype, block):
+    """(dt, state of the loopback layout stepped from Python, state of the one-rank
+    engine) after WIDE_STEPS steps: computed once per case, shared by the IPC
+    (graph, eager) and RCCL tests.  The first is the transports' contract: same
+    kernels, same instantiation, same block lists, the receive buffer filled by
+    ``LoopbackTransport`` (a torch copy of the packed rows).  The second has no
+    receive buffer at all (the plain instantiation of the stage kernel)."""
+    one = _wide_engine(phys, dtype, block)
+    lb = _wide_engine(phys, dtype, block, dt=one.dt, transport=LoopbackTransport)
+    q0 = one.tiles_view().clone()
+    one.step(WIDE_STEPS)
+    lb.step(WIDE_STEPS)
+    torch.cuda.synchronize()
+    assert torch.isfinite(one.tiles_view()).all()
+    assert all(not torch.equal(q0[f], one.tiles_view()[f]) for f in range(q0.shape[0]))      # every column moved
+    return one.dt, lb.tiles_view().clone(), one.tiles_view().clone()
+
+
+def _wide_assert(phys, dtype, block, how, e):
+    """Assertion 1 (the transport's contract), then assertion 2 (the one-rank engine)."""
+    _, lb, one = _wide_reference(phys, dtype, block)
+    got = e.tiles_view()
+    what = f"{how} {phys} {str(dtype).split('.')[-1]} block {block[0]}x{block[1]}"
+    d1 = max(float((got[f] - lb[f]).abs().max() / lb[f].abs().max()) for f in range(got.shape[0]))
+    d2 = max(float((got[f] - one[f]).abs().max() / one[f].abs().max()) for f in range(got.shape[0]))
+    print(f"WIDEROWS {what}: against the loopback layout stepped from Python {d1:.2e}, "
+          f"against one rank {d2:.2e} of the field maximum")
+    for f, name in enumerate(e.physics.fields):
+        assert torch.equal(got[f], lb[f]), f"{what}: field {name} differs from the same layout stepped from Python"
+    for f, name in enumerate(e.physics.fields):
+        assert torch.equal(got[f], one[f]), f"{what}: field {name} differs from the one-rank engine"
+
+
+WIDE_CASES = [pytest.param("trc1", torch.float64, (16, 8), id="trc1-fp64-16x8"),
+              pytest.param("trc3", torch.float64, (16, 8), id="trc3-fp64-16x8"),
+              pytest.param("trc3", torch.float64, (16, 16), id="trc3-fp64-16x16"),
+              pytest.param("trc4", torch.float64, (16, 8), id="trc4-fp64-16x8"),
+              pytest.param("trc1", torch.float32, (16, 8), id="trc1-fp32-16x8"),
+              pytest.param("trc2_ppm", torch.float64, (16, 8), id="trc2_ppm-fp64-16x8"),
+              pytest.param("layers", torch.float64, (16, 8), id="layers-fp64-16x8"),
+              pytest.param("layers", torch.float64, (16, 16), id="layers-fp64-16x16"),
+              pytest.param("layers", torch.float32, (16, 8), id="layers-fp32-16x8")]
+
+
+@pytest.mark.parametrize("use_graph", [True, False], ids=["graph", "eager"])
+@pytest.mark.parametrize("phys,dtype,block", WIDE_CASES)
+def test_ipc_copy_loopback_wide_rows(phys, dtype, block, use_graph):
+    """Tracers and layers through pack (F = 5 .. 8) -> the IPC copy kernel with
+    payloads of ``cnt * F * esize`` bytes and slots sized by F -> the REMOTE
+    instantiation of their stage kernels reading the receive slot: bitwise
+    equal to the same layout stepped from Python, and to the one-rank engine.
+    The loopback plan has one peer at offset 0 and 1920 or 2592 rows, so every
+    payload here is a multiple of 16 bytes (the copy kernel's 16-byte words)."""
+    from stsphere.ops.native_runtime import IpcExchange, NativeStepper
+    dt = _wide_reference(phys, dtype, block)[0]
+    e = _wide_engine(phys, dtype, block, dt=dt, transport=NativeBuffers)
+    ipc = IpcExchange(e, IpcExchange.slots_for(e))
+    try:
+        assert ipc.F == WIDE_F[phys] and ipc.slot_bytes >= e.plan.num_recv * ipc.F * ipc.esize
+        assert list(e.plan.send_offsets) == [0] and e.plan.send_counts[0] * ipc.F * ipc.esize % 16 == 0
+        ns = NativeStepper(e, use_graph=use_graph, steps_per_graph=3, ipc=ipc)
+        try:
+            assert ns.use_graph == use_graph
+            ns.run(WIDE_STEPS)
+            torch.cuda.synchronize()
+            ns.check()
+            if use_graph:
+                assert ns.stats["graph_steps"] >= WIDE_STEPS and ns.stats["eager_steps"] <= 3, ns.stats
+            _wide_assert(phys, dtype, block, "ipc graph" if use_graph else "ipc eager", e)
+        finally:
+            ns.close()
+    finally:
+        ipc.close()
+
+
+@pytest.mark.parametrize("phys,dtype,block", WIDE_CASES)
+def test_rccl_loopback_wide_rows(nccl_comm, phys, dtype, block):
+    """The same cases through the grouped RCCL send / receive with ``slot_elems = F``."""
+    from stsphere.ops.native_runtime import NativeStepper
+    dt = _wide_reference(phys, dtype, block)[0]
+    e = _wide_engine(phys, dtype, block, dt=dt, transport=NativeBuffers)
+    ns = NativeStepper(e, nccl_comm=nccl_comm, use_graph=False, steps_per_graph=3)
+    try:
+        assert not ns.use_graph
+        ns.run(WIDE_STEPS)
+        torch.cuda.synchronize()
+        _wide_assert(phys, dtype, block, "rccl", e)
+    finally:
+        ns.close()

@@ -11,9 +11,11 @@ import torch.multiprocessing as mp
 
 from stsphere.engine import Engine, VirtualCluster
 from stsphere.models.geometry import CubedSphereGrid
-from stsphere.models.swe import ShallowWater
+from stsphere.models.swe import ShallowWater, ShallowWaterTracers
 from stsphere.models.advection import Advection
 from stsphere.parallel.layout import TileLayout
+
+from layer_states import layer_physics
 
 
 # physics axis: the MC-limited default (two ghost layers) and PPM (limiter 4), the
@@ -48,6 +50,36 @@ def test_virtual_ranks_bitwise_equal_single(t, R, phys):
     vc.step(3)
     for f in range(make().F):
         assert np.array_equal(single.global_field(f), vc.global_field(f))
+
+
+# the physics with wider receive rows: tracers ride behind (h, M) (F = 4 + NQ; with
+# PPM mixing ratios three ghost layers), two layers are two shallow-water blocks (F = 8)
+WIDE = {"trc_mc": lambda: ShallowWaterTracers("tc5", tracers=["cap", "cosine_bell"], limiter=2),
+        "trc_ppm": lambda: ShallowWaterTracers("tc5", tracers=["cap"], limiter=2, tracer_limiter="ppm"),
+        "layers": lambda: layer_physics()}
+WIDE_F = {"trc_mc": (6, 2), "trc_ppm": (5, 3), "layers": (8, 2)}        # (F, ghost layers)
+
+
+def _wide_start(phys, N):
+    """The rough start state [F, 6, N, N] of a WIDE physics (tracer_states.py,
+    layer_states.py): the cap and the cosine bell are zero on most of the
+    sphere, the rough states have signal in every column at every rank boundary."""
+    if phys == "layers":
+        from layer_states import global_state
+        return global_state(N, "rough")
+    from tracer_states import global_state
+    return global_state(WIDE_F[phys][0] - 4, N, "rough")
+
+
+def _wide_single(phys, N, t, steps=3):
+    from rough_states import install
+    make = WIDE[phys]
+    F, ng = WIDE_F[phys]
+    assert (make().F, make().halo) == (F, ng)
+    single = Engine(make(), TileLayout(N, t, 1, ng=ng), grid=CubedSphereGrid(N), dt=300.0)
+    install(single, _wide_start(phys, N))
+    single.step(steps)
+    return single
 
 
 def _free_port():
@@ -100,6 +132,88 @@ def _gloo_equals_single(N, world, t, staged, limiter):
     for f in range(4):
         glob = assemble_global(L, {r: np.load(os.path.join(out, f"r{r}.npy"))[f] for r in range(world)})
         assert np.array_equal(glob, single.global_field(f))
+
+
+def _worker_wide(rank, world, port, N, t, staged, outdir, phys):
+    import torch.distributed as dist
+    from rough_states import install
+    from stsphere.parallel.comm import TorchDistTransport
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        ph = WIDE[phys]()
+        L = TileLayout(N, t, world, ng=ph.halo)
+        tr = TorchDistTransport(L.plan(rank), ph.F, torch.float64, torch.device("cpu"), staged=staged)
+        e = Engine(ph, L, rank, transport=tr, dt=300.0)
+        install(e, _wide_start(phys, N))
+        e.step(3)
+        np.save(os.path.join(outdir, f"r{rank}.npy"), e.tiles_view().numpy())
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("phys,world,t,staged", [("trc_mc", 2, 1, False), ("trc_mc", 3, 1, True), ("trc_mc", 4, 2, False),
+                                                 ("trc_ppm", 2, 2, False), ("trc_ppm", 3, 1, False), ("trc_ppm", 4, 2, True),
+                                                 ("layers", 2, 1, True), ("layers", 3, 1, False), ("layers", 4, 2, False)])
+def test_gloo_multiprocess_equals_single_wide_rows(phys, world, t, staged, tmp_path):
+    """Receive rows of 5, 6 and 8 values through real messages, from the rough
+    states: every field of every rank count bitwise equal to one rank.  N = 12:
+    the PPM tracers' carried corners need n >= 2 ng at t = 2."""
+    from stsphere.engine import assemble_global
+    N = 12
+    out = str(tmp_path)
+    mp.spawn(_worker_wide, args=(world, _free_port(), N, t, staged, out, phys), nprocs=world, join=True)
+    single = _wide_single(phys, N, t)
+    F, ng = WIDE_F[phys]
+    L = TileLayout(N, t, world, ng=ng)
+    for f in range(F):
+        glob = assemble_global(L, {r: np.load(os.path.join(out, f"r{r}.npy"))[f] for r in range(world)})
+        assert np.isfinite(glob).all() and np.array_equal(glob, single.global_field(f)), (phys, f)
+
+
+def _wide_loopback(phys, t, N=12, steps=3):
+    """The loopback engine of a WIDE physics after ``steps`` steps from the rough state."""
+    from rough_states import install
+    from stsphere.parallel.comm import LoopbackTransport
+    F, ng = WIDE_F[phys]
+    L = TileLayout(N, t, 1, ng=ng, loopback=True)
+    p = L.plan(0)
+    assert p.recv_peers == [0] and (p.ghost_map < 0).all() and p.ghost_map.shape[2] == ng
+    lb = Engine(WIDE[phys](), L, grid=CubedSphereGrid(N), dt=300.0,
+                transport=LoopbackTransport(p, F, torch.float64, torch.device("cpu")))
+    assert lb.transport.recv.shape == (p.num_recv, F)
+    install(lb, _wide_start(phys, N))
+    lb.step(steps)
+    return lb
+
+
+@pytest.mark.parametrize("phys,t", [("trc_mc", 2), ("trc_mc", 1), ("trc_ppm", 2), ("trc_ppm", 1), ("layers", 2), ("layers", 1)])
+def test_loopback_layout_equals_single_wide_rows(phys, t):
+    """Every ghost of every column comes out of a receive buffer with rows of F = 5, 6 or 8 values."""
+    single, lb = _wide_single(phys, 12, t), _wide_loopback(phys, t)
+    for f in range(WIDE_F[phys][0]):
+        assert torch.equal(single.tiles_view()[f], lb.tiles_view()[f]), (phys, single.physics.fields[f])
+
+
+@pytest.mark.parametrize("phys,cols", [("trc_mc", (4, 5)), ("layers", (0, 4))])
+def test_loopback_comparison_notices_a_misplaced_column(phys, cols, monkeypatch):
+    """The comparison above is sensitive to what it is there for: with two
+    columns of the receive buffer swapped on delivery (hq_0 and hq_1; h_0 and
+    h_1) both fields differ from one rank, after one step already."""
+    from stsphere.parallel.comm import LoopbackTransport
+    finish = LoopbackTransport.finish
+
+    def swapped(self):
+        recv = finish(self)
+        recv[:, list(cols)] = recv[:, list(cols[::-1])]
+        return recv
+
+    single = _wide_single(phys, 12, 2, steps=1)
+    monkeypatch.setattr(LoopbackTransport, "finish", swapped)
+    lb = _wide_loopback(phys, 2, steps=1)
+    for f in cols:
+        assert torch.isfinite(lb.tiles_view()[f]).all()
+        assert not torch.equal(single.tiles_view()[f], lb.tiles_view()[f]), (phys, single.physics.fields[f])
 
 
 def test_loopback_layout_equals_single():

@@ -23,7 +23,7 @@ from stsphere.engine import Engine
 from stsphere.models.swe import ShallowWaterTracers
 from stsphere.parallel.layout import TileLayout
 
-TRACER_SETS = {1: ["cap"], 2: ["cap", "cosine_bell"], 4: ["cap", "cosine_bell", "gradient", "constant"]}
+TRACER_SETS = {1: ["cap"], 2: ["cap", "cosine_bell"], 3: ["cap", "cosine_bell", "gradient"], 4: ["cap", "cosine_bell", "gradient", "constant"]}
 
 
 def rough_mixing_ratios(nq: int, N: int, seed: int = 0) -> torch.Tensor:
