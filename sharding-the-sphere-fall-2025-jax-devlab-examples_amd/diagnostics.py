@@ -280,6 +280,22 @@ class SolverDiagnostics:
         return self._gather_tiles({e.rank: y[0].detach().cpu().numpy()
                                    for e, y in zip(self.engines, laplacian_all(ds, xs))})
 
+    def helmholtz(self, field, tau: float, tol: float = 1e-10, maxiter: int = 500) -> np.ndarray:
+        """x [6, N, N] float64 with (I - tau L) x = ``field`` [6, N, N], L the consistent
+        Laplacian (``ops.heat.HeatOperator.solve``: BiCGStab, on the device with the HIP
+        backend); the solve's record is kept as ``helmholtz_record``.  One rank.  Like
+        ``laplacian``, it serves every model with one scalar field (the operator is built on
+        first use); the shallow-water model raises ``ValueError``."""
+        if self.mode != "single":
+            raise ValueError("helmholtz: one rank only (the solve's inner products would need a fold across ranks)")
+        e = self.engines[0]
+        f = np.asarray(field, dtype=np.float64)
+        if f.shape != (6, self.layout.N, self.layout.N):
+            raise ValueError(f"helmholtz: a field of shape {(6, self.layout.N, self.layout.N)} expected, not {f.shape}")
+        b = torch.as_tensor(e.geo.gather_global(f), dtype=torch.float64, device=e.device)
+        x, self.helmholtz_record = e.heat_operator().solve(b, tau, tol=tol, maxiter=maxiter)
+        return self._gather_tiles({e.rank: x.detach().cpu().numpy()})
+
     # ---- lat-lon output (models/latlon.py, ops/latlon.py) ---------------------------
     def latlon_names(self) -> List[str]:
         """What ``latlon_field`` / ``zonal_mean`` accept for this model."""

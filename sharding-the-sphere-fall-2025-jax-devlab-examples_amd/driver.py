@@ -35,7 +35,7 @@ from .engine import Engine, VirtualCluster
 from .models.advection import Advection
 from .models.base import limiter_code
 from .models.derived import FIELDS as DERIVED_FIELDS, INVARIANTS
-from .models.diffusion import OPERATORS, ConsistentDiffusion, Diffusion
+from .models.diffusion import OPERATORS, ConsistentDiffusion, Diffusion, implicit_spec
 from .models.geometry import DAY, EARTH_RADIUS, CubedSphereGrid
 from .models.spectra import check_lmax
 from .models.swe import MAX_TRACERS, LayeredShallowWater, ShallowWater, ShallowWaterTracers
@@ -88,6 +88,9 @@ def make_physics(pc) -> Any:
         raise ValueError(f"physics.operator: one of {list(OPERATORS)} expected, not {op!r}")
     if op == "consistent" and model != "diffusion":
         raise ValueError(f"physics.operator: consistent is defined for the diffusion model, not {model!r}")
+    if implicit_spec(getattr(pc, "implicit", None)) is not None and (model != "diffusion" or op != "consistent"):
+        raise ValueError(f"physics.implicit: defined for the diffusion model with operator: consistent, not "
+                         f"{model!r} with operator: {op}")
     flow, period_days = getattr(pc, "flow", None), getattr(pc, "period_days", None)
     if (flow is not None or period_days is not None) and model != "advection":
         raise ValueError(f"physics.flow / physics.period_days: the prescribed wind of the advection model, "
@@ -291,6 +294,8 @@ class Solver(SolverDiagnostics):
         self._dspec = None            # physics.dissipation, checked (initialize)
         self._dinterval = 0           # model steps between its applications (doubles when dt is halved)
         self._gstepper = None         # engine.GraphStepper of a time-dependent physics (one GPU, runtime.graph)
+        self._ispec = None            # physics.implicit, checked (initialize)
+        self.implicit_iterations: List[int] = []      # BiCGStab iterations of every implicit step so far
 
     # ---- setup ------------------------------------------------------------
     def setup_sharding(self) -> None:
@@ -322,6 +327,10 @@ class Solver(SolverDiagnostics):
         if c.physics.operator == "consistent" and self.world > 1:
             raise ValueError("physics.operator: consistent: one process per rank (spmd) is not supported; run one "
                              "rank or virtual ranks in one process")
+        self._ispec = implicit_spec(c.physics.implicit)
+        if self._ispec is not None and nd > 1:
+            raise ValueError("physics.implicit: virtual ranks are not supported (the solve's inner products would "
+                             "need a fold across ranks); run one rank (num_devices: 1)")
         gpu = c.parallelization.device_type == "gpu"
         if gpu and not torch.cuda.is_available():
             raise RuntimeError("device_type 'gpu' requested but no GPU is visible (use device_type: cpu)")
@@ -429,6 +438,9 @@ class Solver(SolverDiagnostics):
                 raise ValueError(f"io.spectra: {err}") from None
         self._log(f"Initialized {phys0.name} ({getattr(phys0, 'case', '')}) C{N}, {self.mode} mode, "
                   f"backend={backend}, dtype={c.grid.dtype}, dt={dt:.3f} s, integrator={c.time.integrator}")
+        if self._ispec is not None:
+            self._log(f"Implicit diffusion: theta = {self._ispec['theta']:g}, one BiCGStab Helmholtz solve per step "
+                      f"(tol {self._ispec['tol']:g}); time.integrator is ignored")
         if c.io.initial_condition and not c.io.restore:
             self._initial_condition_stage(c.io.initial_condition)
         if c.io.restore:
@@ -766,7 +778,12 @@ class Solver(SolverDiagnostics):
         return apply_all(ds, self._dinterval * self.dt if tau is None else float(tau))
 
     def _step_model(self, nsteps: int) -> None:
-        if self.mode == "virtual":
+        if self._ispec is not None:
+            op, s = self.engines[0].heat_operator(), self._ispec
+            for _ in range(nsteps):
+                rec = op.implicit_step(self.dt, self.physics.kappa, s["theta"], s["tol"], s["maxiter"])
+                self.implicit_iterations.append(rec["iterations"])
+        elif self.mode == "virtual":
             self.cluster.step(nsteps)
         elif self._use_native():
             if self.runner is None:
@@ -1026,6 +1043,9 @@ class Solver(SolverDiagnostics):
                    "kernel_launches": (self.runner.stats["launches"] if self.runner is not None else 0),
                    "phase_s": dict(ph.times)}
         summary.update(self.diagnostics())
+        if self._ispec is not None and self.implicit_iterations:
+            its = self.implicit_iterations[-done:] if done else []
+            summary["implicit_iterations"] = {"mean": float(np.mean(its)) if its else 0.0, "max": max(its, default=0)}
         if self.physics.time_dependent:      # the deformational-flow tests: extrema and the mass against the start
             q = self.global_field(0)
             if q is not None:

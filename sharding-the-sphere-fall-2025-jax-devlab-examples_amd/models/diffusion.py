@@ -20,6 +20,7 @@ through ``Physics.rhs``: ``ops/heat.py`` drives it, and ``heat_gradient_pass``,
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -147,3 +148,76 @@ def heat_stage(L: torch.Tensor, st, dt: float, kappa: float, X: torch.Tensor, Q:
     if st.a0 != 0.0:
         out = out + st.a0 * f(X)
     return out, acc
+
+
+# ---- the twin of ops/csrc/helmholtz_kernel.hip ------------------------------------------------
+
+HELM_CONVERGED, HELM_BREAKDOWN = 1, 2      # the flag of a solve's record (0: neither yet)
+THETAS = (1.0, 0.5)                        # physics.implicit.theta: backward Euler, Crank-Nicolson
+
+
+def implicit_spec(d) -> Optional[Dict[str, float]]:
+    """``physics.implicit`` checked and completed: {theta, tol, maxiter}, or None when it is off."""
+    if d is None:
+        return None
+    if not isinstance(d, dict) or set(d) - {"theta", "tol", "maxiter"}:
+        raise ValueError(f"physics.implicit: {{theta, tol, maxiter}} expected, not {d!r}")
+    theta, tol, maxiter = d.get("theta", 1.0), d.get("tol", 1e-10), d.get("maxiter", 500)
+    try:                                         # YAML 1.1 reads 1e-10 (no dot) as a string
+        theta, tol = float(theta), float(tol)
+    except (TypeError, ValueError):
+        raise ValueError(f"physics.implicit: theta and tol must be numbers, not {d!r}") from None
+    if theta not in THETAS:
+        raise ValueError(f"physics.implicit.theta: 1.0 (backward Euler) or 0.5 (Crank-Nicolson) expected, not {theta!r}")
+    if not tol > 0 or isinstance(maxiter, bool) or not isinstance(maxiter, int) or maxiter < 1:
+        raise ValueError(f"physics.implicit: tol > 0 and an integer maxiter >= 1 expected, not {d!r}")
+    return {"theta": theta, "tol": tol, "maxiter": maxiter}
+
+
+def helmholtz_bicgstab(lap, area: torch.Tensor, b: torch.Tensor, x: torch.Tensor, tau: float, tol: float,
+                       maxiter: int) -> Tuple[torch.Tensor, Dict[str, float]]:
+    """(I - tau L) x = b by unpreconditioned BiCGStab from the first guess ``x``, float64:
+    the recurrences, their association and the flag rules of ``helmholtz_kernel.hip``
+    (only the order in which an inner product's terms are added differs: ``sum`` here, a
+    fixed tree there).  ``lap(u)``: L u [T, n, n]; inner products are area weighted,
+    (u, w) = sum((area u) w).  Returns (x, {iterations, residual, flag}); after a flag is
+    set x is not touched again."""
+    dot = lambda u, w: float(((area * u) * w).sum())
+    A = lambda u: u - tau * lap(u)
+    r = b - A(x)
+    rh, p = r.clone(), r.clone()
+    rho, bb = dot(r, r), dot(b, b)
+    rnorm, bnorm = math.sqrt(rho) if rho >= 0 else math.nan, math.sqrt(bb) if bb >= 0 else math.nan
+    it = 0
+    flag = HELM_BREAKDOWN if not (math.isfinite(rho) and math.isfinite(bb)) else (
+        HELM_CONVERGED if rnorm <= tol * bnorm else 0)
+    while not flag and it < maxiter:
+        v = A(p)
+        den = dot(rh, v)
+        if den == 0.0 or not math.isfinite(den) or not math.isfinite(rho):
+            flag = HELM_BREAKDOWN
+            break
+        alpha = rho / den
+        s = r - alpha * v
+        t = A(s)
+        ts, tt = dot(t, s), dot(t, t)
+        if not (math.isfinite(ts) and math.isfinite(tt)):
+            flag = HELM_BREAKDOWN
+            break
+        omega = 0.0 if tt == 0.0 else ts / tt
+        x = (x + alpha * p) + omega * s
+        r = s - omega * t
+        rho1, rr = dot(rh, r), dot(r, r)
+        it += 1
+        rnorm = math.sqrt(rr) if rr >= 0 else math.nan
+        if not (math.isfinite(rho1) and math.isfinite(rr)):
+            flag = HELM_BREAKDOWN
+        elif rnorm <= tol * bnorm:
+            flag = HELM_CONVERGED
+        elif rho == 0.0 or omega == 0.0:
+            flag = HELM_BREAKDOWN
+        else:
+            beta = (rho1 / rho) * (alpha / omega)
+            rho = rho1
+            p = r + beta * (p - omega * v)
+    return x, {"iterations": it, "residual": rnorm / bnorm if bnorm > 0.0 else rnorm, "flag": flag}

@@ -418,6 +418,40 @@ typedef struct HeatDesc {
 } HeatDesc;
 int stsp_heat_launch(int dtype, const HeatDesc* d, hipStream_t stream);
 int stsp_heat_desc_size(void);
+// Helmholtz solve (I - tau L) x = b with the consistent Laplacian L of the heat
+// kernels (helmholtz_kernel.hip, ops/heat.py::HeatOperator.solve; the twin:
+// models/diffusion.py::helmholtz_bicgstab): unpreconditioned BiCGStab whose scalars
+// live in `block` on the device.  op 0: r = b - A x, rhat = p = r, the first rho,
+// ||b|| and the flags (3 launches); op 1: `iters` iterations (10 launches each),
+// every kernel of which returns at once when a flag is set.  One rank without
+// remote ghosts.  Everything is float64.
+#define STSP_HELM_ROWS 8        // work rows: x, r, rhat, p, v, s, t, b
+#define STSP_HELM_BLOCK 10      // doubles of the scalar block (HelmBlock, helmholtz_kernel.hip)
+#define STSP_HELM_RECORD 8      // the 16-byte record starts at this double: relres, then int flags, int iters
+#define STSP_HELM_CONVERGED 1   // flags
+#define STSP_HELM_BREAKDOWN 2
+#define STSP_HELM_MAX_ITERS 64  // most iterations of one op 1 call
+typedef struct HelmDesc {
+  double* work;         // [8][S] x, r, rhat, p, v, s, t, b, padded layout; interior cells are read and written
+  double* scratch;      // [4][S] of the gradient pass: the iterate, Gx, Gy, Gz
+  const int* gmap;      // [T][4][mg][n]; layer 0 is read; every code >= 0 (an interior cell of this rank)
+  const double* W;      // the tables of HeatDesc
+  const double* cx;
+  const double* cy;
+  const double* kx;
+  const double* ky;
+  const double* invA;
+  double* partials;     // [2][nblocks] block sums of the inner products
+  double* block;        // [10] the scalar block
+  int ntile, n, S, mg, pw;   // S = ntile * pw * pw, pw = n + 2 mg
+  int nblocks;          // ntile * ceil(n / 16)^2
+  int op;               // 0 set up, 1 iterate
+  int iters;            // op 1: iterations to launch, 1 .. STSP_HELM_MAX_ITERS
+  double tau;
+  double tol;           // op 0: converged once ||r|| <= tol ||b||
+} HelmDesc;
+int stsp_helmholtz_launch(const HelmDesc* d, hipStream_t stream);
+int stsp_helmholtz_desc_size(void);
 // Ensemble statistics of one field of a batched state (ensemble_kernel.hip,
 // ops/ensemble_stats.py; definitions and the twin in models/ensemble_stats.py):
 // a launch with one workgroup per 16 x 16 cell block (mean and population

@@ -19,12 +19,19 @@ same-rank ghost slots of the new state by one indexed copy, so that they equal
 their source cells as the output products expect.  One process per rank (spmd)
 is not supported.
 
+``HeatOperator.solve(b, tau)`` solves the Helmholtz problem (I - tau L) x = b, the
+building block of the implicit steps (``implicit_step``: backward Euler and
+Crank-Nicolson, ``physics.implicit``), by BiCGStab: with ``backend='hip'`` the
+device-resident iteration of ``ops/csrc/helmholtz_kernel.hip``, else its twin
+``models.diffusion.helmholtz_bicgstab``.
+
 All shape contracts the kernels rely on are checked here, on the host, once,
 before anything is launched.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -54,6 +61,23 @@ class HeatDesc(ctypes.Structure):
     ]
 
 
+class HelmDesc(ctypes.Structure):
+    """Mirror of HelmDesc (stsp_kernels.h)."""
+    _fields_ = [
+        ("work", ctypes.c_void_p), ("scratch", ctypes.c_void_p), ("gmap", ctypes.c_void_p), ("W", ctypes.c_void_p),
+        ("cx", ctypes.c_void_p), ("cy", ctypes.c_void_p), ("kx", ctypes.c_void_p), ("ky", ctypes.c_void_p),
+        ("invA", ctypes.c_void_p), ("partials", ctypes.c_void_p), ("block", ctypes.c_void_p),
+        ("ntile", ctypes.c_int), ("n", ctypes.c_int), ("S", ctypes.c_int), ("mg", ctypes.c_int), ("pw", ctypes.c_int),
+        ("nblocks", ctypes.c_int), ("op", ctypes.c_int), ("iters", ctypes.c_int),
+        ("tau", ctypes.c_double), ("tol", ctypes.c_double),
+    ]
+
+
+# stsp_kernels.h: STSP_HELM_ROWS, STSP_HELM_BLOCK, STSP_HELM_RECORD, STSP_HELM_MAX_ITERS
+HELM_ROWS, HELM_BLOCK, HELM_RECORD, HELM_MAX_CHUNK = 8, 10, 8, 64
+RX, RR, RH, RP, RV, RS, RT, RB = range(HELM_ROWS)
+
+
 def _library():
     """The native library with the heat entry points declared and the
     descriptor's size compared with the mirror's."""
@@ -66,6 +90,12 @@ def _library():
                                f"{lib.stsp_heat_desc_size()} (stale libstsp.so?)")
         lib.stsp_heat_launch.argtypes = [ctypes.c_int, ctypes.POINTER(HeatDesc), ctypes.c_void_p]
         lib.stsp_heat_launch.restype = ctypes.c_int
+        lib.stsp_helmholtz_desc_size.argtypes, lib.stsp_helmholtz_desc_size.restype = [], ctypes.c_int
+        if lib.stsp_helmholtz_desc_size() != ctypes.sizeof(HelmDesc):
+            raise RuntimeError(f"HelmDesc: ctypes mirror is {ctypes.sizeof(HelmDesc)} bytes, the library's "
+                               f"{lib.stsp_helmholtz_desc_size()} (stale libstsp.so?)")
+        lib.stsp_helmholtz_launch.argtypes = [ctypes.POINTER(HelmDesc), ctypes.c_void_p]
+        lib.stsp_helmholtz_launch.restype = ctypes.c_int
         lib._heat_declared = True
     return lib
 
@@ -99,6 +129,7 @@ class HeatOperator:
         self.lout = torch.zeros((1, self.S), **f64)
         self.tr_scratch = _transport(e, mh.HEAT_ROWS, torch.float64) if plan.num_recv else None
         self.hip = use_hip(e)
+        self.work = None              # the solver's rows, blocks and descriptor: built by the first solve
         if self.hip:
             self._setup_kernel()
 
@@ -237,6 +268,127 @@ class HeatOperator:
     def laplacian(self) -> torch.Tensor:
         """L [T, n, n] (float64) of the engine's state (one rank)."""
         return laplacian_all([self])[0]
+
+    # ---- the Helmholtz solve ------------------------------------------------------------------------
+    def _setup_solver(self) -> None:
+        """The work rows [8, S] (x, r, rhat, p, v, s, t, b; float64, padded layout), and for
+        the kernels the partials, the scalar block, the pinned record and the descriptor,
+        with the shape contracts of ``helmholtz_kernel.hip`` checked."""
+        e, plan = self.e, self.e.plan
+        if plan.num_recv:
+            raise ValueError("HeatOperator.solve: a rank with remote ghosts (virtual ranks): the inner products "
+                             "of the iteration would need a fold across ranks; run one rank")
+        if self.work is not None:
+            return
+        f64 = dict(dtype=torch.float64, device=e.device)
+        self.area = 1.0 / self.tabs["invA"]
+        work = torch.zeros((HELM_ROWS, self.S), **f64)
+        if self.hip:
+            from . import native
+            self.partials = torch.zeros((2, self.nblocks), **f64)
+            self.block = torch.zeros((HELM_BLOCK,), **f64)
+            self.record = torch.zeros((HELM_BLOCK - HELM_RECORD,), dtype=torch.float64, pin_memory=True)
+            assert work.shape == (HELM_ROWS, self.S) and work.is_contiguous() and work.is_cuda
+            assert self.partials.is_contiguous() and self.block.is_contiguous()
+            assert self.record.numel() * 8 == 16
+            gm = plan.ghost_map                      # every neighbour across a tile side is a cell of this rank
+            assert gm.size == 0 or (gm.min() >= 0 and gm.max() < self.S)
+            d, h = HelmDesc(), self.desc
+            d.work, d.partials, d.block = native.ptr(work), native.ptr(self.partials), native.ptr(self.block)
+            for k in ("scratch", "gmap", "W", "cx", "cy", "kx", "ky", "invA", "ntile", "n", "S", "mg", "pw", "nblocks"):
+                setattr(d, k, getattr(h, k))
+            self.hdesc = d
+        self.work = work
+
+    def _row(self, r: int) -> torch.Tensor:
+        """Interior view [T, n, n] of work row ``r``."""
+        return self.e.interior(self.work[r:r + 1])[0]
+
+    def _twin_laplacian(self, u: torch.Tensor) -> torch.Tensor:
+        """L u [T, n, n] by the twin's two passes (row t of the work rows stages u)."""
+        e = self.e
+        self._row(RT).copy_(u)
+        mh.heat_gradient_pass(self.work[RT:RT + 1], None, e.gmap, self.tabs, self.T, self.n, self.ng, self.scratch)
+        return mh.heat_flux_pass(self.scratch, None, e.gmap, self.tabs, self.T, self.n, self.ng)
+
+    def _launch_solver(self, op: int, iters: int, tau: float, tol: float) -> dict:
+        """One call of the entry point (op 0: set up, 1: ``iters`` iterations), then the
+        16-byte record: the only device-to-host traffic of a chunk."""
+        from . import native
+        d = self.hdesc
+        d.op, d.iters, d.tau, d.tol = op, iters, tau, tol
+        native.check(self.lib.stsp_helmholtz_launch(d, native.current_stream_handle(self.e.device)),
+                     "helmholtz kernels")
+        self.record.copy_(self.block[HELM_RECORD:], non_blocking=True)
+        torch.cuda.current_stream(self.e.device).synchronize()
+        flags, iters = self.record.numpy().view(np.int32)[2:4]
+        return {"iterations": int(iters), "residual": float(self.record[0]), "flag": int(flags)}
+
+    def solve(self, b: torch.Tensor, tau: float, x0: Optional[torch.Tensor] = None, tol: float = 1e-10,
+              maxiter: int = 500, chunk: int = 8, out: Optional[torch.Tensor] = None):
+        """x with (I - tau L) x = b, by unpreconditioned BiCGStab (L is not symmetric).
+
+        ``b`` and ``x0`` (default: zero) are interior values [T, n, n] of any floating
+        type; the iteration is float64 throughout and x is rounded once, to ``b``'s type
+        (or copied into ``out``, an interior view, and rounded to its type).  Returns (x,
+        record) with record = {iterations, residual: ||r|| / ||b|| in the area-weighted
+        norm, flag: ``models.diffusion.HELM_CONVERGED``}.  With the kernels the scalars stay
+        on the device: ``chunk`` iterations are launched at a time on the caller's stream,
+        and the record is read back after each chunk.
+
+        Raises ``RuntimeError`` (with the record as ``.record``) on a breakdown or when
+        ``maxiter`` iterations do not reach ``||r|| <= tol ||b||``; the work row x then holds
+        the last iterate.  One rank: a rank with remote ghosts (virtual ranks) raises
+        ``ValueError``, because the inner products would need a fold across ranks."""
+        shape = (self.T, self.n, self.n)
+        tau, tol = float(tau), float(tol)
+        if tuple(b.shape) != shape or (x0 is not None and tuple(x0.shape) != shape):
+            raise ValueError(f"HeatOperator.solve: b and x0 of shape {shape} expected, not {tuple(b.shape)}")
+        if not (math.isfinite(tau) and tol >= 0.0 and maxiter >= 1 and 1 <= chunk <= HELM_MAX_CHUNK):
+            raise ValueError(f"HeatOperator.solve: finite tau, tol >= 0, maxiter >= 1 and 1 <= chunk <= "
+                             f"{HELM_MAX_CHUNK} expected, not tau={tau}, tol={tol}, maxiter={maxiter}, chunk={chunk}")
+        self._setup_solver()
+        self._row(RB).copy_(b)
+        if x0 is None:
+            self._row(RX).zero_()
+        else:
+            self._row(RX).copy_(x0)
+        if self.hip:
+            rec = self._launch_solver(0, 0, tau, tol)
+            while not rec["flag"] and rec["iterations"] < maxiter:
+                rec = self._launch_solver(1, min(chunk, maxiter - rec["iterations"]), tau, tol)
+        else:
+            x, rec = mh.helmholtz_bicgstab(self._twin_laplacian, self.area, self._row(RB).clone(),
+                                           self._row(RX).clone(), tau, tol, maxiter)
+            self._row(RX).copy_(x)
+        if rec["flag"] != mh.HELM_CONVERGED:
+            err = RuntimeError(f"HeatOperator.solve: " + ("breakdown" if rec["flag"] else "no convergence") +
+                               f" after {rec['iterations']} iterations, ||r|| / ||b|| = {rec['residual']:.3e} "
+                               f"(tol {tol:g}, tau {tau:g})")
+            err.record = rec
+            raise err
+        if out is None:
+            out = torch.empty(shape, dtype=b.dtype, device=b.device)
+        out.copy_(self._row(RX))
+        return out, rec
+
+    def implicit_step(self, dt: float, kappa: float, theta: float, tol: float = 1e-10, maxiter: int = 500) -> dict:
+        """One step of the theta scheme on the engine's state,
+
+            (I - theta dt kappa L) T' = T + (1 - theta) dt kappa L T,
+
+        backward Euler (theta = 1) or Crank-Nicolson (1/2): the right-hand side from the two
+        passes, the solve from T as the first guess; returns the solve's record."""
+        e = self.e
+        Ti = e.interior(e.state)[0]
+        b = Ti.to(torch.float64)
+        if theta != 1.0:
+            b = b + ((1.0 - theta) * dt * kappa) * self.laplacian()
+        _, rec = self.solve(b, theta * dt * kappa, x0=Ti, tol=tol, maxiter=maxiter, out=Ti)
+        self.refresh(e.state)
+        e.time += dt
+        e._step_count += 1
+        return rec
 
 
 def laplacian_all(ops: Sequence[HeatOperator]) -> List[torch.Tensor]:

@@ -63,6 +63,11 @@ class PhysicsConfig:
     # refinement); consistent: the corrected flux of models/dissipation.py (second
     # order, conservative, not monotone; two launches per stage, eager stepping)
     operator: str = "two_point"
+    # diffusion with operator: consistent only: implicit time stepping by a Helmholtz
+    # solve per step (BiCGStab on the device, ops/heat.py::HeatOperator.solve):
+    # {theta: 1.0 (backward Euler) | 0.5 (Crank-Nicolson), tol: 1e-10, maxiter: 500};
+    # time.dt is taken as given and time.integrator is ignored; one rank; null = explicit
+    implicit: Optional[Dict[str, Any]] = None
     # shallow water only: initial conditions of up to 4 passive tracers carried by
     # the flow (models/initial_conditions.py::tracer_field: constant | cosine_bell |
     # cap | gradient); null or empty = none
