@@ -37,6 +37,7 @@ from .models.base import limiter_code
 from .models.derived import FIELDS as DERIVED_FIELDS, INVARIANTS
 from .models.diffusion import OPERATORS, ConsistentDiffusion, Diffusion, implicit_spec
 from .models.geometry import DAY, EARTH_RADIUS, CubedSphereGrid
+from .models.initial_conditions import LAYER_CASES, STACK_CASES, STACK_MAX_LAYERS
 from .models.spectra import check_lmax
 from .models.swe import MAX_TRACERS, LayeredShallowWater, ShallowWater, ShallowWaterTracers
 from .parallel.comm import NativeBuffers, TorchDistTransport
@@ -143,10 +144,17 @@ def layers_spec(pc) -> Optional[Dict[str, Any]]:
         except (TypeError, ValueError):
             raise ValueError(f"physics.layers.{key}: a list of numbers expected, not {v!r}") from None
     out: Dict[str, Any] = {"depths": numbers("depths", d["depths"])}
-    if len(out["depths"]) != 2:
-        raise ValueError(f"physics.layers.depths: two layers [H_0, H_1] expected, not {d['depths']!r}")
+    nl = len(out["depths"])
+    if not 2 <= nl <= STACK_MAX_LAYERS:
+        raise ValueError(f"physics.layers.depths: 2 to {STACK_MAX_LAYERS} layers [H_0, H_1, ..] expected, "
+                         f"not {d['depths']!r}")
+    if nl > 2 and pc.case in LAYER_CASES and pc.case not in STACK_CASES:
+        raise ValueError(f"physics.layers: case {pc.case!r} is defined for two layers, not {nl}; "
+                         f"{nl} layers take {list(STACK_CASES)}")
     if d.get("winds") is not None:
         out["winds"] = numbers("winds", d["winds"])
+        if len(out["winds"]) != nl:
+            raise ValueError(f"physics.layers.winds: one number per layer ({nl}) expected, not {d['winds']!r}")
     for key in ("density_ratio", "jet_scale"):
         if d.get(key) is not None:
             out[key] = numbers(key, [d[key]])[0]

@@ -345,6 +345,88 @@ def layered_fields(case, p, depths=None, density_ratio=0.9, winds=None, jet_scal
     return h, wind, b
 
 
+# ---- three and more layers --------------------------------------------------------
+STACK_CASES = ("tc2", "rest", "tc5")
+STACK_MAX_LAYERS = 8           # the layer-streaming stage kernel's ceiling
+
+
+def stack_winds(L):
+    """Default ``tc2`` winds of L layers: ``LAYER_WINDS`` continued with its step."""
+    return [LAYER_WINDS[0] + k * (LAYER_WINDS[1] - LAYER_WINDS[0]) for k in range(L)]
+
+
+def montgomery_drops(A, density_ratio):
+    """d of  W d = A:  W[k][j] = r^(k-j) for j < k (the layers above press with
+    their density ratio), 1 else.  With h_k = H_k - d_k s^2 / g the Montgomery
+    height b + c_k + h_k of layer k falls by A_k s^2 / g, which balances a
+    solid-body rotation of speed U_k, A_k = R Omega U_k + U_k^2 / 2.  Two layers:
+    d_0 = (A_0 - A_1) / (1 - r)."""
+    L, r = len(A), float(density_ratio)
+    W = np.array([[r ** (k - j) if j < k else 1.0 for j in range(L)] for k in range(L)])
+    return np.linalg.solve(W, np.asarray(A, dtype=np.float64))
+
+
+def stacked_fields(case, p, depths, density_ratio=0.9, winds=None, alpha=0.0,
+                   radius=EARTH_RADIUS, omega=OMEGA, g=GRAVITY):
+    """L >= 2 layers of resting depths ``depths`` with one ratio r =
+    ``density_ratio`` between adjacent layers.  Returns (h [L, ...], wind
+    [L, ..., 3], b).  (``layered_fields`` keeps the two-layer runs; for two
+    layers both give the same fields up to rounding.)
+
+    * ``rest``  uniform layers, no wind;
+    * ``tc2``   exact steady state: layer k in solid-body rotation U_k =
+      winds[k] u0, h_k = H_k - d_k s^2 / g with ``montgomery_drops``;
+    * ``tc5``   every layer at TC5's u0 over its mountain: equal A_k make every
+      d_k zero but the last, so the upper layers are flat and
+      h_{L-1} = H_{L-1} - (R Omega u0 + u0^2 / 2) sin^2(lat) / g - b.
+
+    The jet cases are built from one interface and stay two-layer.  Parameters
+    that make a thickness non-positive are refused."""
+    L = len(depths)
+    if case in LAYER_CASES and case not in STACK_CASES:
+        raise ValueError(f"layered shallow water: case {case!r} is defined for two layers, not {L}; "
+                         f"{L} layers take {list(STACK_CASES)}")
+    if case not in STACK_CASES:
+        raise ValueError(f"unknown layered shallow-water case {case!r}; choose from {list(STACK_CASES)}")
+    if L < 2 or not all(float(H) > 0 for H in depths):
+        raise ValueError(f"layered shallow water: depths = [H_0, H_1, ..], all positive, expected, "
+                         f"not {list(depths)!r}")
+    H = [float(x) for x in depths]
+    r = float(density_ratio)
+    if not 0.0 < r < 1.0:
+        raise ValueError(f"layered shallow water: density_ratio = rho_k / rho_(k+1) in (0, 1) expected, not {r!r}")
+    lon, lat = xyz_to_lonlat(p)
+    zero = np.zeros(p.shape[:-1])
+    b = zero
+    if case == "rest":
+        h = np.stack([zero + Hk for Hk in H])
+        wind = np.zeros((L,) + p.shape)
+    elif case == "tc2":
+        winds = stack_winds(L) if winds is None else winds
+        if len(winds) != L:
+            raise ValueError(f"layered shallow water: winds = one number per layer ({L}) expected, "
+                             f"not {list(winds)!r}")
+        u0 = 2.0 * math.pi * radius / (12.0 * DAY)
+        U = [float(w) * u0 for w in winds]
+        d = montgomery_drops([radius * omega * u + 0.5 * u * u for u in U], r)
+        s = -np.cos(lon) * np.cos(lat) * math.sin(alpha) + np.sin(lat) * math.cos(alpha)
+        h = np.stack([H[k] - d[k] * s * s / g for k in range(L)])
+        wind = np.stack([solid_body_wind(p, u, alpha, radius) for u in U])
+    else:
+        u0 = 20.0
+        b = tc5_mountain(p)
+        hb = H[-1] - (radius * omega * u0 + 0.5 * u0 * u0) * np.sin(lat) ** 2 / g - b
+        h = np.stack([zero + Hk for Hk in H[:-1]] + [hb])
+        w = solid_body_wind(p, u0, 0.0, radius)
+        wind = np.stack([w] * L)
+    for k in range(L):
+        if not h[k].min() > 0:
+            raise ValueError(f"layered shallow water, case {case!r}: the thickness of layer {k} is not positive "
+                             f"(minimum {h[k].min():.6g} m) with depths {H}, density_ratio {r}; "
+                             f"use deeper layers, weaker winds or a smaller density_ratio")
+    return h, wind, b
+
+
 # ----------------------------------------------------------------------------
 # Deformational flows (Nair & Lauritzen 2010; Lauritzen et al. 2012): prescribed
 # winds that depend on time, reverse at t = T / 2 and return the tracer to its

@@ -325,7 +325,8 @@ class LayeredShallowWater(ShallowWater):
 
     ``depths``: resting depths [H_0, ..]; None = one layer with the case's own
     depth (the parent's cases).  Two layers take the cases of
-    ``initial_conditions.layered_fields``; more than two only ``rest``.
+    ``initial_conditions.layered_fields``; more than two ``rest``, ``tc2`` and
+    ``tc5`` of ``initial_conditions.stacked_fields`` (``winds``: one per layer).
     ``density_ratio`` r = rho_k / rho_{k+1} of adjacent layers.
 
     Diagnostics: mass_k = sum(h_k A) and one energy
@@ -351,8 +352,15 @@ class LayeredShallowWater(ShallowWater):
         self.jet_scale = None if jet_scale is None else float(jet_scale)
         if self.nl == 2 and case not in ic.LAYER_CASES:
             raise ValueError(f"unknown layered shallow-water case {case!r}; choose from {list(ic.LAYER_CASES)}")
-        if self.nl > 2 and case != "rest":
-            raise ValueError(f"layered shallow water with {self.nl} layers has the case 'rest' only, not {case!r}")
+        if self.nl > 2:
+            if case in ic.LAYER_CASES and case not in ic.STACK_CASES:
+                raise ValueError(f"layered shallow water: case {case!r} is defined for two layers, not {self.nl}; "
+                                 f"{self.nl} layers take {list(ic.STACK_CASES)}")
+            if case not in ic.STACK_CASES:
+                raise ValueError(f"unknown layered shallow-water case {case!r}; choose from {list(ic.STACK_CASES)}")
+            if self.winds is not None and len(self.winds) != self.nl:
+                raise ValueError(f"layered shallow water: winds = one number per layer ({self.nl}) expected, "
+                                 f"not {self.winds!r}")
         L = self.nl
         self.rho = [self.density_ratio ** (L - 1 - k) for k in range(L)]     # relative to the bottom layer
         # coupling weights: c_k = sum_j cw[k][j] h_j
@@ -370,8 +378,8 @@ class LayeredShallowWater(ShallowWater):
         if self.nl == 2:
             return ic.layered_fields(self.case, p, self.depths, self.density_ratio, self.winds, self.jet_scale,
                                      alpha=self.alpha, radius=grid.radius, omega=self.omega, g=self.g)
-        zero = np.zeros(p.shape[:-1])
-        return np.stack([zero + H for H in self.depths]), np.zeros((self.nl,) + p.shape), zero
+        return ic.stacked_fields(self.case, p, self.depths, self.density_ratio, self.winds,
+                                 alpha=self.alpha, radius=grid.radius, omega=self.omega, g=self.g)
 
     def layer_fields(self, grid: CubedSphereGrid):
         """(h [L, 6, N, N], wind [L, 6, N, N, 3], b) for any L."""

@@ -18,8 +18,11 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libstsp.so")
-SOURCES = ["stage_kernel.hip", "march_kernel.hip", "march3_kernel.hip", "swe_tracer_stage.hip", "swe_layer_stage.hip", "fused_step.hip", "derived_kernel.hip", "dissipation_kernel.hip", "heat_kernel.hip", "helmholtz_kernel.hip", "wind_kernel.hip", "ensemble_kernel.hip", "latlon_kernel.hip", "points_kernel.hip", "spectra_kernel.hip", "synth_kernel.hip", "tt_kernels.hip", "tt_persist.hip", "runtime.cpp"]
+SOURCES = ["stage_kernel.hip", "march_kernel.hip", "march3_kernel.hip", "swe_tracer_stage.hip", "swe_layer_stage.hip", "swe_layers_stream.hip", "fused_step.hip", "derived_kernel.hip", "dissipation_kernel.hip", "heat_kernel.hip", "helmholtz_kernel.hip", "wind_kernel.hip", "ensemble_kernel.hip", "latlon_kernel.hip", "points_kernel.hip", "spectra_kernel.hip", "synth_kernel.hip", "tt_kernels.hip", "tt_persist.hip", "runtime.cpp"]
 HEADERS = ["stsp_kernels.h", "stage_common.h", "xg_ring.h", "xg_codec.h", "march_common.h", "tt_common.h", "runtime.h", "rccl_abi.h"]
+# extra compile flags of single sources: the layer-streaming kernel is built
+# without the packed fp32 instructions (v_pk_*_f32)
+SOURCE_FLAGS = {"swe_layers_stream.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 ARCH = os.environ.get("STSP_OFFLOAD_ARCH", "gfx950")
 # library variants: "" = production; "diag" = in-kernel phase stamps of the
 # stage kernel (-DSTSP_STAMPS); the others are A/B
@@ -95,7 +98,7 @@ def build(force: bool = False, verbose: bool = False, variant: str = "") -> str:
         objs.append(op)
         if not force and os.path.exists(op) and os.path.getmtime(op) >= max(os.path.getmtime(sp), hdr_t):
             continue
-        cmd = [_hipcc(), *flags, "-c", sp, "-o", op + ".tmp"]
+        cmd = [_hipcc(), *flags, *SOURCE_FLAGS.get(src, []), "-c", sp, "-o", op + ".tmp"]
         if verbose:
             print(" ".join(cmd))
         procs.append((op, cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

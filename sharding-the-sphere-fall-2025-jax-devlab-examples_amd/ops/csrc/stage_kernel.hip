@@ -1027,9 +1027,11 @@ extern "C" int stsp_swe_tracer_launch(int dtype, int bx, int by, const StageDesc
 
 // bx == 64: the streaming shallow-water stage (march_kernel.hip), by = rows per wave;
 // phys == 3: shallow water with tracers (swe_tracer_stage.hip);
-// phys == 4: two-layer shallow water (swe_layer_stage.hip)
+// phys == 4: two-layer shallow water (swe_layer_stage.hip); with more than two
+// layers the layer-streaming kernel (swe_layers_stream.hip)
 extern "C" int stsp_stage_launch(int phys, int dtype, int bx, int by, const StageDesc* d, hipStream_t stream) {
   if (phys == 3) return stsp_swe_tracer_launch(dtype, bx, by, d, stream);
+  if (phys == 4 && d->layers > 2) return stsp_swe_layers_stream_launch(dtype, bx, by, d, stream);
   if (phys == 4) return stsp_swe_layer_launch(dtype, bx, by, d, stream);
   if (bx == 64) return phys == 2 ? stsp_march_launch(dtype, by, d, stream) : -2;
   if (dtype == 1) return launch_d<double>(phys, bx, by, d, stream);

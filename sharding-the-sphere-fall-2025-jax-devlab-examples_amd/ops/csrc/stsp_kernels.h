@@ -76,6 +76,8 @@ typedef struct StageDesc {
                         // (interface values confined between their cells; needs mg >= 3)
   double layer_r;       // two-layer shallow water (phys 4, swe_layer_stage.hip): density ratio rho_0 / rho_1
                         // in (0, 1]; the state holds F = 8 fields (h_0, M_0, h_1, M_1) and recv is [R][8]
+  int layers;           // phys 4: layers L of the stack.  0 or 2: the two-layer kernel; 3 .. 8: the layer-streaming
+                        // kernel (swe_layers_stream.hip), layer_r the ratio of adjacent layers, F = 4 L, recv [R][4 L]
 } StageDesc;
 
 int stsp_stage_launch(int phys, int dtype, int bx, int by, const StageDesc* d, hipStream_t stream);
@@ -96,6 +98,12 @@ int stsp_stage_batch_launch(int phys, int dtype, int bx, int by, const StageDesc
 int stsp_swe_layer_launch(int dtype, int bx, int by, const StageDesc* d, hipStream_t stream);
 // dynamic LDS bytes of one of its blocks (-1: unsupported shape); a launch over 65536 is refused with -13
 int stsp_swe_layer_lds(int dtype, int bx, int by);
+// N-layer shallow water, 3 <= d->layers <= 8 (swe_layers_stream.hip): one RK stage, the stack streamed through a
+// one-layer window; stsp_stage_launch routes phys 4 with layers > 2 here.  The codes of stsp_swe_layer_launch, and
+//   -18  d->layers outside 3 .. 8
+int stsp_swe_layers_stream_launch(int dtype, int bx, int by, const StageDesc* d, hipStream_t stream);
+// dynamic LDS bytes of one of its blocks, the same for every L (-1: unsupported shape)
+int stsp_swe_layers_stream_lds(int dtype, int bx, int by);
 // Pipelined streaming SSP-RK3 step (march3_kernel.hip): one launch marches all
 // three stages up each strip of a tile (stage s + 1 trails stage s by two rows),
 // reading the step input d->Q once and writing the step output d->out at the

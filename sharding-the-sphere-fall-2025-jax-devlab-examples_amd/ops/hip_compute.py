@@ -27,7 +27,7 @@ BLOCK_SHAPES = ((16, 16), (32, 8), (16, 8), (8, 16), (8, 8))
 MARCH_SHAPES = ((64, 4), (64, 8), (64, 16), (64, 32))
 # Shallow water with tracers (physics 3, ops/csrc/swe_tracer_stage.hip)
 TRACER_SHAPES = ((16, 16), (16, 8))
-# Two-layer shallow water (physics 4, ops/csrc/swe_layer_stage.hip)
+# Layered shallow water (physics 4: two layers ops/csrc/swe_layer_stage.hip, three to eight swe_layers_stream.hip)
 LAYER_SHAPES = ((16, 16), (16, 8))
 SWE_KERNELS = (2, 3, 4)   # physics ids that read the SWE geometry (mx, my, cgeo)
 
@@ -213,14 +213,34 @@ def layer_lds_bytes(bx: int, by: int, esize: int = 8) -> int:
     return (9 * wf + 5 * ne + 2 * 8 * 4 * bm + 3 * (bx + by + 2) + ne) * esize
 
 
-def choose_layer_block(n: int, tiles: int = 0, cus: int = 0, esize: int = 8):
-    """Block shape of the two-layer stage kernel, among ``LAYER_SHAPES`` by the
+LAYERS_STREAM_MIN, LAYERS_STREAM_MAX = 3, 8    # layers of the layer-streaming kernel (two: swe_layer_stage.hip)
+
+
+def layers_stream_lds_bytes(bx: int, by: int, esize: int = 8, layers: int = 3) -> int:
+    """Dynamic LDS of one block of the layer-streaming stage kernel
+    (swe_layers_stream.hip, ``LsGeom::ELEMS * sizeof(T)``; the library exports
+    the same number as ``stsp_swe_layers_stream_lds`` and ``HipCompute`` checks
+    the two agree): the window of ONE layer's four primitives and the sqrt(g H)
+    row, five flux rows, the panel-edge rows of one layer (neighbour's edge
+    state, raw cell, raw strips), normals and edge lengths.  The stack streams
+    through the window and the column sums live in registers, so the count does
+    not depend on ``layers``."""
+    ne = (bx + 1) * by + bx * (by + 1)
+    wf = (by + 4) * (bx + 4 + 1)
+    bm, em = max(bx, by), max(bx, by) + 4
+    return (5 * wf + 5 * ne + 2 * 4 * 4 * bm + 4 * 4 * em + 3 * (bx + by + 2) + ne) * esize
+
+
+def choose_layer_block(n: int, tiles: int = 0, cus: int = 0, esize: int = 8, layers: int = 2):
+    """Block shape of the layer stage kernels, among ``LAYER_SHAPES`` by the
     rule of ``choose_tracer_block``: 16 x 16 while its grid fits the compute
     units in one pass and the 16 x 8 grid does not (and its launch fits in
-    ``LAYER_LDS_MAX``), else 16 x 8."""
+    ``LAYER_LDS_MAX``: ``layer_lds_bytes`` for two layers,
+    ``layers_stream_lds_bytes`` above), else 16 x 8."""
     def count(bx, by):
         return tiles * -(-n // bx) * -(-n // by)
-    if tiles and cus and count(16, 16) <= cus < count(16, 8) and layer_lds_bytes(16, 16, esize) <= LAYER_LDS_MAX:
+    lds = layer_lds_bytes(16, 16, esize) if layers <= 2 else layers_stream_lds_bytes(16, 16, esize, layers)
+    if tiles and cus and count(16, 16) <= cus < count(16, 8) and lds <= LAYER_LDS_MAX:
         return (16, 16)
     return (16, 8)
 
@@ -245,7 +265,8 @@ class HipCompute:
                 bx, by = choose_tracer_block(n, T, cus, int(kp["nq"]), torch.tensor([], dtype=e.dtype).element_size(),
                                              int(kp.get("tracer_limiter", 0)))
             elif self.phys_id == 4:
-                bx, by = choose_layer_block(n, T, cus, torch.tensor([], dtype=e.dtype).element_size())
+                bx, by = choose_layer_block(n, T, cus, torch.tensor([], dtype=e.dtype).element_size(),
+                                            int(phys.kernel_params()["layers"]))
             else:
                 bx, by = choose_block(n, T, cus, getattr(phys, "limiter", 0), torch.tensor([], dtype=e.dtype).element_size())
             # streaming stage once the rank streams: measured C720 (3.1M cells, 12k per CU)
@@ -322,21 +343,27 @@ class HipCompute:
                                  f"{' on PPM' if self._tlim == 4 else ''} needs {lds} bytes of LDS per block, "
                                  f"more than the {TRACER_LDS_MAX} a launch gets; use block (16, 8)")
         self._layer_r = 0.0
-        if self.phys_id == 4:      # (h_0, M_0, h_1, M_1): the kernel strides the state and the receive buffer by 8
+        self._layers = 0
+        if self.phys_id == 4:      # (h_k, M_k) of L layers: the kernels stride the state and the receive buffer by 4 L
             kp = phys.kernel_params()
-            if int(kp["layers"]) != 2:
-                raise ValueError(f"the layer stage kernel runs two layers, not {int(kp['layers'])} "
+            nl = self._layers = int(kp["layers"])
+            if nl < 2 or nl > LAYERS_STREAM_MAX:
+                raise ValueError(f"the layer stage kernels run 2 to {LAYERS_STREAM_MAX} layers, not {nl} "
                                  f"(backend='torch' takes any number)")
-            assert F == 8, "two-layer state: (h, M) of each layer"
+            assert F == 4 * nl, "layered state: (h, M) of each layer"
             assert 0 <= int(kp.get("limiter", 0)) <= 3, "the layer stage kernel has the PLR limiters 0 to 3"
             self._layer_r = float(kp["layer_r"])
             assert 0.0 < self._layer_r <= 1.0, "layer stage kernel: density ratio rho_0 / rho_1 in (0, 1]"
             assert plan.ng >= 2 and "pedge" in t and "pe_base" in t
-            self.lib.stsp_swe_layer_lds.argtypes = [ctypes.c_int] * 3
-            self.lib.stsp_swe_layer_lds.restype = ctypes.c_int
-            lds = int(self.lib.stsp_swe_layer_lds(self.dcode, bx, by))
             esize = torch.tensor([], dtype=e.dtype).element_size()
-            assert lds == layer_lds_bytes(bx, by, esize), "layer stage kernel: LDS size rule"
+            if nl == 2:            # swe_layer_stage.hip: both layers resident
+                lds_fn, rule = self.lib.stsp_swe_layer_lds, layer_lds_bytes(bx, by, esize)
+            else:                  # swe_layers_stream.hip: the stack streams through a one-layer window
+                lds_fn, rule = self.lib.stsp_swe_layers_stream_lds, layers_stream_lds_bytes(bx, by, esize, nl)
+            lds_fn.argtypes = [ctypes.c_int] * 3
+            lds_fn.restype = ctypes.c_int
+            lds = int(lds_fn(self.dcode, bx, by))
+            assert lds == rule, "layer stage kernel: LDS size rule"
             if lds > LAYER_LDS_MAX:
                 raise ValueError(f"layer stage kernel: block {(bx, by)} needs {lds} bytes of LDS per block, "
                                  f"more than the {LAYER_LDS_MAX} a launch gets; use block (16, 8)")
@@ -436,6 +463,7 @@ class HipCompute:
         d.nq = self._nq
         d.tracer_limiter = self._tlim
         d.layer_r = self._layer_r
+        d.layers = self._layers
         if "pedge" in t:
             d.pedge = p(t["pedge"])
         if "pe_base" in t:

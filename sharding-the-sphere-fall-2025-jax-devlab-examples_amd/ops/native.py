@@ -48,6 +48,8 @@ class StageDesc(ctypes.Structure):
         ("nq", ctypes.c_int), ("tracer_limiter", ctypes.c_int),
         # two-layer shallow water (swe_layer_stage.hip)
         ("layer_r", ctypes.c_double),
+        # layers of the stack: above two, the layer-streaming kernel (swe_layers_stream.hip)
+        ("layers", ctypes.c_int),
     ]
 
 

@@ -13,6 +13,12 @@ one, and the least bytes a step moves per cell (every stage reads and writes
 its fields once: 8 against 4).  Two layers are expected to cost about two plain
 steps; the ratio is reported, nothing is gated on it.
 
+``--layers 3,4,8`` adds one row per L of the layer-streaming kernel
+(ops/csrc/swe_layers_stream.hip), interleaved with the two above, with its time
+per layer against the two-layer kernel's (``per_layer_ratio_to_layers2``).  The
+streaming kernel reads every depth twice per stage: ``bytes_with_second_h_read``
+counts that, F + L values read and F written per cell and stage.
+
     python tools/layers_probe.py                      # C96 and C360
     python tools/layers_probe.py --sizes 96x2 --block 16,16
 """
@@ -33,6 +39,7 @@ def main():
     ap.add_argument("--reps", type=int, default=50, help="steps per timed window")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--warm", type=int, default=10)
+    ap.add_argument("--layers", default="", help="layer counts (3 .. 8) of the layer-streaming kernel, comma separated")
     a = ap.parse_args()
     import torch
     from stsphere.engine import Engine, GraphStepper
@@ -50,6 +57,9 @@ def main():
         mk = lambda p: Engine(p, L, grid=grid, device="cuda", backend="hip", block=block)   # noqa: E731
         eng = {"swe": mk(ShallowWater("tc5", limiter=2)),
                "layers2": mk(LayeredShallowWater("tc5", depths=[2000.0, 5960.0], density_ratio=0.9, limiter=2))}
+        for nl in (int(v) for v in a.layers.split(",") if v):
+            depths = [2000.0] * (nl - 1) + [5960.0]
+            eng[f"layers{nl}"] = mk(LayeredShallowWater("tc5", depths=depths, density_ratio=0.9, limiter=2))
         run = {}
         dt = min(e.dt for e in eng.values())
         for k, e in eng.items():
@@ -78,6 +88,10 @@ def main():
             rec[k] = {"us_per_step": round(med, 2), "min": round(min(ts[k]), 2), "max": round(max(ts[k]), 2),
                       "ratio_to_swe": round(med / base, 3), "fields": F,
                       "min_bytes_per_cell_step": 2 * F * esize * stages, "byte_ratio_to_swe": F / 4}
+            if F > 8:
+                rec[k]["us_per_layer"] = round(med / (F // 4), 2)
+                rec[k]["per_layer_ratio_to_layers2"] = round(med / (F // 4) / (statistics.median(ts["layers2"]) / 2), 3)
+                rec[k]["bytes_with_second_h_read"] = (2 * F + F // 4) * esize * stages
         print(json.dumps(rec), flush=True)
 
 
