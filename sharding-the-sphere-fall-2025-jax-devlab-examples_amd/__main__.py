@@ -25,7 +25,8 @@
                                                        a history field analysed to degree LMAX and synthesised
                                                        back on the cells (--band: degrees LMIN .. LCUT only), or
                                                        the streamfunction / velocity_potential of a
-                                                       shallow-water history, on the CPU
+                                                       shallow-water history, or its rotational_wind /
+                                                       divergent_wind (arrays u, v), on the CPU
     ensemble CONFIG.yaml [--members M] [--amplitude A] [--days D | --nsteps K] [--batched]
                                                        perturbed members of one config on one device
                                                        (--batched: every member's stage in one launch)
@@ -164,7 +165,7 @@ def main(argv=None):
         import numpy as np
         r = synth_history(a.history, a.field, a.lmax, band=a.band)
         np.savez(a.out, **r)
-        print(json.dumps({"out": a.out, "field": a.field, "shape": list(r["field"].shape)}))
+        print(json.dumps({"out": a.out, "field": a.field, "shape": list(r["field" if "field" in r else "u"].shape)}))
         return 0
     if a.cmd == "regrid":
         import numpy as np
@@ -342,7 +343,9 @@ def synth_history(history: str, field: str, lmax: int, band=None) -> dict:
     with the PyTorch twin on the CPU (models/spectra.py): field [frames, 6, N, N],
     time.  ``streamfunction`` / ``velocity_potential``: psi / chi (m^2 / s) from
     the h, mx, my, mz of a shallow-water history (vorticity and divergence by
-    the derived-field twin)."""
+    the derived-field twin); ``rotational_wind`` / ``divergent_wind``: k x grad psi
+    / grad chi of the same psi, chi as u, v [frames, 6, N, N] (m / s) instead of
+    field, by the gradient twin."""
     import numpy as np
     import torch
     from .models import spectra as ms
@@ -352,7 +355,8 @@ def synth_history(history: str, field: str, lmax: int, band=None) -> dict:
     if field in ("u", "v") and field not in have:
         raise ValueError(f"{field!r} is a vector component, not a scalar on the sphere; use the fields "
                          f"'streamfunction' and 'velocity_potential' for the winds")
-    hel = field in ("streamfunction", "velocity_potential") and field not in have
+    wind = field in ("rotational_wind", "divergent_wind") and field not in have
+    hel = wind or (field in ("streamfunction", "velocity_potential") and field not in have)
     need = ["h", "mx", "my", "mz"] if hel else [field]
     missing = [f for f in need if f not in have]
     if missing:
@@ -371,12 +375,19 @@ def synth_history(history: str, field: str, lmax: int, band=None) -> dict:
         from .parallel.layout import TileLayout
         e = Engine(ShallowWater((cfg.get("physics") or {}).get("case") or "tc5"), TileLayout(N, 1, 1, ng=2), grid=grid)
         sp = e.spectra(lmax)
-        which = 0 if field == "streamfunction" else 1
+        which = 0 if field in ("streamfunction", "rotational_wind") else 1
         for fr in torch.as_tensor(np.ascontiguousarray(src, dtype=np.float64)):
             e.set_state(fr)
             c = sp.partial_tiles(e.derived()[0][:2])
             co = ms.scale_degrees(ms.helmholtz(c[0], c[1], radius)[which], fac)
-            out.append(sp.synthesise(co[None])[0])
+            if wind:
+                g = ms.gradient(co[None], sp.tab, radius)[0].reshape(2, 6, N, N)
+                out.append(torch.stack([-g[1], g[0]]) if which == 0 else g)
+            else:
+                out.append(sp.synthesise(co[None])[0])
+        if wind:
+            uv = torch.stack(out).numpy()
+            return {"u": uv[:, 0], "v": uv[:, 1], "time": zarr_lite.read_array(history, "time")}
     else:
         tb = ms.grid_tables(grid, lmax)
         for fr in torch.as_tensor(np.ascontiguousarray(src, dtype=np.float64)):

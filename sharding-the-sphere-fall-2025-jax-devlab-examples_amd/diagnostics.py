@@ -618,6 +618,78 @@ class SolverDiagnostics:
         ``streamfunction``."""
         return self._psi_chi(lmax, 1, "velocity potential")
 
+    # ---- gradient synthesis: rotational and divergent winds ------------------------------------
+    def _gradient(self, coeffs, lmax: int) -> Optional[np.ndarray]:
+        """[C, 2, 6, N, N] float64 (east, north) on rank 0 (None elsewhere) of
+        the coefficients [C, 2, L+1, L+1] that rank 0 holds; the ranks work as
+        in ``_synthesise``.  Collective under SPMD."""
+        sps = [e.spectra(lmax) for e in self.engines]
+        if self.mode == "spmd":
+            import torch.distributed as dist
+            box = [coeffs.detach().cpu().numpy() if self.rank == 0 else None]
+            dist.broadcast_object_list(box, src=0)
+            coeffs = torch.as_tensor(box[0])
+        C = coeffs.shape[0]
+        vals = {}
+        for e, sp in zip(self.engines, sps):
+            g = sp.gradient(coeffs.contiguous())
+            vals[e.rank] = g.reshape((2 * C,) + tuple(g.shape[2:])).detach().cpu().numpy()
+        r = self._gather_tiles(vals)
+        return None if r is None else r.reshape((C, 2) + r.shape[1:])
+
+    def gradient(self, coeffs) -> Optional[np.ndarray]:
+        """The horizontal gradient (per metre) of the band-limited field of
+        given coefficients on the solver's own cells, in each cell's local
+        (east, north) frame: [2, 6, N, N] for ``coeffs`` [2, L+1, L+1], [C, 2, 6,
+        N, N] for [C, 2, L+1, L+1]; float64, on rank 0 (None elsewhere).  Every
+        rank passes the same array.  Entries with m > l and S_l0 are not read."""
+        co = torch.as_tensor(np.asarray(coeffs, dtype=np.float64))
+        one = co.dim() == 3
+        if one:
+            co = co[None]
+        if co.dim() != 4 or co.shape[0] < 1 or co.shape[1] != 2 or co.shape[2] != co.shape[3]:
+            raise ValueError(f"gradient: coefficients [2, L+1, L+1] or [C, 2, L+1, L+1] expected, "
+                             f"not {tuple(np.shape(coeffs))}")
+        lmax = check_lmax(int(co.shape[2]) - 1, self.layout.N)
+        r = self._gradient(co.to(self.engines[0].device), lmax)
+        return None if r is None else (r[0] if one else r)
+
+    def _winds(self, lmax: int, what: str, lmin: int = 0, lcut: Optional[int] = None):
+        """(rot, div) [2, 6, N, N] (u, v) each on rank 0, None elsewhere: the
+        gradients of psi and chi with the degrees ``lmin .. lcut`` kept."""
+        if self.physics.name != "swe":
+            raise ValueError(f"the {what} is defined for the shallow-water model, "
+                             f"not {self.physics.name!r}")
+        lmax = check_lmax(lmax, self.layout.N)
+        band = spectra_band(lmax, lmin, lcut)
+        r = self._spectra_coeffs(["vorticity", "divergence"], lmax)
+        co = None
+        if r is not None:
+            co = spectra_scale(torch.stack(spectra_helmholtz(r[0], r[1], self.grid.radius)), band.to(r.device))
+        g = self._gradient(co, lmax)
+        if g is None:
+            return None
+        return np.stack([-g[0, 1], g[0, 0]]), g[1]
+
+    def rotational_wind(self, lmax: int) -> Optional[np.ndarray]:
+        """[2, 6, N, N] (u, v) in m/s: the rotational part k x grad psi of the
+        wind to degree ``lmax``, psi as in ``streamfunction``; on rank 0 (None
+        elsewhere)."""
+        r = self._winds(lmax, "rotational wind")
+        return None if r is None else r[0]
+
+    def divergent_wind(self, lmax: int) -> Optional[np.ndarray]:
+        """[2, 6, N, N] (u, v) in m/s: the divergent part grad chi, like
+        ``rotational_wind``."""
+        r = self._winds(lmax, "divergent wind")
+        return None if r is None else r[1]
+
+    def band_wind(self, lmax: int, lmin: int = 0, lcut: Optional[int] = None) -> Optional[np.ndarray]:
+        """[2, 6, N, N] (u, v) in m/s: rotational plus divergent wind of the
+        degrees ``lmin .. lcut`` (default: up to ``lmax``) of psi and chi."""
+        r = self._winds(lmax, "band-passed wind", lmin, lcut)
+        return None if r is None else r[0] + r[1]
+
     def invariants(self) -> Dict[str, float]:
         """mass, energy, potential_enstrophy, circulation, abs_circulation
         (sums over the sphere) and max_courant (maximum) of the current state."""

@@ -351,3 +351,132 @@ def clean_coeffs(coeffs: torch.Tensor) -> torch.Tensor:
     co = torch.tril(coeffs)
     co[:, 1, :, 0] = 0.0
     return co
+
+
+# ----------------------------------------------------------------------------
+# gradient synthesis: rotational and divergent winds, and what
+# ops/csrc/grad_synth_kernel.hip reads
+# ----------------------------------------------------------------------------
+# The physical gradient of f = sum P_lm(mu) (C_lm cos m lam + S_lm sin m lam) at a cell:
+#   east  = (1 / (R cos phi)) df/dlam,   north = (1 / R) df/dphi
+# in the frame of the cell's table longitude, e_east = (-sin lam, cos lam, 0) and
+# e_north = (-sin phi cos lam, -sin phi sin lam, cos phi); a cell centre on a pole has
+# lam = atan2(0, 0) = 0 and the result is the finite vector in that frame.  Nothing
+# divides by cos phi: for m >= 1 the column Q_lm = P_lm / cos phi comes out of the same
+# recurrence (a, b unchanged) started from Q_mm = c_m cos^(m-1) phi, and
+#   east    += m sum_l Q_lm (S_lm cos m lam - C_lm sin m lam)
+#   dP_lm/dphi = f_lm Q_(l-1)m - l mu Q_lm,   f_lm = sqrt((l^2 - m^2)(2l + 1) / (2l - 1))
+#   dP_l0/dphi = sqrt(l (l+1) / 2) P_l1 = sqrt(l (l+1) / 2) cos phi Q_l1.
+# With v = k x grad psi + grad chi:  u = -north(psi) + east(chi),  v = east(psi) + north(chi).
+
+GRAD_CHANNELS = 2         # 6 columns per channel, and one of order 0's per channel: 14 of 16
+
+
+def shift_factors(lmax: int) -> np.ndarray:
+    """f [L+1, L+1] float64: f[l, m] = sqrt((l^2 - m^2)(2l + 1) / (2l - 1)) for l > m, 0 elsewhere."""
+    L = int(lmax)
+    l = np.arange(L + 1, dtype=np.float64)[:, None]
+    m = np.arange(L + 1, dtype=np.float64)[None, :]
+    ok = l > m
+    return np.where(ok, np.sqrt(np.where(ok, (l * l - m * m) * (2.0 * l + 1.0), 0.0) / np.where(ok, 2.0 * l - 1.0, 1.0)),
+                    0.0)
+
+
+def gradient(coeffs: torch.Tensor, tb: SpectraTables, radius: float) -> torch.Tensor:
+    """[C, 2, cells] float64 (east, north) of the gradient of the band-limited
+    fields of ``coeffs`` [C, 2, L+1, L+1] at the cell centres.  Termwise: the
+    derivative rows D_lm = dP_lm/dphi are built and multiplied.  Entries with
+    m > l and S_l0 are not read."""
+    C, L = coeffs.shape[0], tb.lmax
+    assert coeffs.shape == (C, 2, L + 1, L + 1)
+    dev = coeffs.device
+    mu, cphi, lam = tb.cell[:, 0], tb.cell[:, 1], tb.cell[:, 2]
+    co = clean_coeffs(coeffs.to(torch.float64))
+    out = torch.zeros((C, 2, tb.cells), dtype=torch.float64, device=dev)
+    f = torch.as_tensor(shift_factors(L), device=dev)
+    deg = torch.arange(L + 1, dtype=torch.float64, device=dev)
+    for m in range(1, L + 1):
+        qmm = tb.c[m] * cphi ** (m - 1)
+        rows = [qmm]
+        p1, p2 = qmm, torch.zeros_like(qmm)
+        for l in range(m + 1, L + 1):
+            p = tb.a[l, m] * (mu * p1 - tb.b[l, m] * p2)
+            rows.append(p)
+            p1, p2 = p, p1
+        Q = torch.stack(rows)                                        # rows l = m .. L
+        below = torch.cat([torch.zeros_like(Q[:1]), Q[:-1]])          # Q_(l-1)m, 0 at l = m
+        D = f[m:, m, None] * below - deg[m:, None] * mu * Q
+        cs, sn = torch.cos(m * lam), torch.sin(m * lam)
+        Cm, Sm = co[:, 0, m:, m], co[:, 1, m:, m]
+        out[:, 0] += m * ((Sm @ Q) * cs - (Cm @ Q) * sn)
+        out[:, 1] += (Cm @ D) * cs + (Sm @ D) * sn
+        if m == 1:
+            D0 = torch.sqrt(deg[1:, None] * (deg[1:, None] + 1.0) / 2.0) * cphi * Q
+            out[:, 1] += co[:, 0, 1:, 0] @ D0
+    return out / radius
+
+
+def winds(psi: torch.Tensor, chi: torch.Tensor, tb: SpectraTables, radius: float):
+    """(rot [2, cells], div [2, cells]) as (u, v): k x grad psi and grad chi of
+    the coefficients ``psi``, ``chi`` [2, L+1, L+1]."""
+    g = gradient(torch.stack([psi, chi]), tb, radius)
+    return torch.stack([-g[0, 1], g[0, 0]]), g[1]
+
+
+def grad_rows(lmax: int) -> int:
+    return lmax * (lmax + 1) // 2
+
+
+def grad_pack_tables(lmax: int, device="cpu"):
+    """What ``pack_gradient`` needs besides the coefficients, on ``device``: (l, m,
+    l1, lf, fs, rider): the rows' degree and order (long [R]), min(l + 1, L), l as
+    float64, f_(l+1)m (0 at l = L) and sqrt(l (l+1) / 2) for l = 1 .. L."""
+    L = int(lmax)
+    l, m = (x[L + 1:] for x in pack_index(L))
+    lf, mf = l.astype(np.float64), m.astype(np.float64)
+    fs = np.where(l < L, np.sqrt((lf + 1.0 - mf) * (lf + 1.0 + mf) * (2.0 * lf + 3.0) / (2.0 * lf + 1.0)), 0.0)
+    d = np.arange(1, L + 1, dtype=np.float64)
+    return tuple(torch.as_tensor(x, device=device)
+                 for x in (l, m, np.minimum(l + 1, L), lf, fs, np.sqrt(d * (d + 1.0) / 2.0)))
+
+
+def pack_gradient(coeffs: torch.Tensor, tables=None) -> torch.Tensor:
+    """What the gradient kernel reads: [L (L+1) / 2, 16] float64, rows (m >= 1,
+    l >= m) in order of m then l (the rows of ``pack_index`` behind order 0's).
+    Channel ch holds columns 6 ch .. 6 ch + 5 = K^c, K^s, l K^c, l K^s,
+    f_(l+1)m K^c_(l+1)m, f_(l+1)m K^s_(l+1)m (0 at l = L); in the rows of order 1
+    column 12 + ch = sqrt(l (l+1) / 2) C_l0; the others 0.  A gather of the lower
+    triangle on the coefficients' device (the l = L rows gather (L, m) again,
+    times 0: finite coefficients expected).  ``tables``: ``grad_pack_tables`` on
+    that device, when the caller keeps them."""
+    C, L = coeffs.shape[0], coeffs.shape[-1] - 1
+    assert coeffs.shape == (C, 2, L + 1, L + 1) and 1 <= C <= GRAD_CHANNELS and coeffs.dtype == torch.float64
+    l, m, l1, lf, fs, rider = grad_pack_tables(L, coeffs.device) if tables is None else tables
+    R = l.shape[0]
+    out = torch.zeros((R, 2 * MAX_CHANNELS), dtype=torch.float64, device=coeffs.device)
+    if R == 0:
+        return out
+    K = coeffs[:, :, l, m]                                            # [C, 2, R]
+    six = torch.cat([K, K * lf, coeffs[:, :, l1, m] * fs], 1)         # [C, 6, R]
+    out[:, :6 * C] = six.permute(2, 0, 1).reshape(R, 6 * C)
+    out[:L, 12:12 + C] = (coeffs[:, 0, 1:, 0] * rider).T              # order 1 is the first L rows
+    return out
+
+
+def grad_chunk_bounds(lmax: int, chunks: int) -> list:
+    """[chunks + 1] first order of each chunk of the gradient launch, 1 = b[0] <
+    b[1] < ... < b[chunks] = L + 1 over the orders 1 .. L: contiguous, none
+    empty, about equal numbers of rows each (order m has L + 1 - m)."""
+    L = int(lmax)
+    if not isinstance(chunks, (int, np.integer)) or isinstance(chunks, bool) or not 1 <= chunks <= max(L, 1):
+        raise ValueError(f"chunks = {chunks!r} outside 1 .. {max(L, 1)}")
+    total = grad_rows(L)
+    b, m, done = [1], 1, 0
+    for k in range(1, chunks):
+        m, done = m + 1, done + (L + 1 - m)
+        while done * chunks < k * total and m < L + 1 - (chunks - k):
+            done += L + 1 - m
+            m += 1
+        b.append(m)
+    b.append(L + 1)
+    return b

@@ -318,6 +318,33 @@ typedef struct SynthDesc {
 } SynthDesc;
 int stsp_synth_launch(const SynthDesc* d, hipStream_t stream);
 int stsp_synth_desc_size(void);
+// Gradient synthesis (grad_synth_kernel.hip, ops/spectra.py; definitions, the
+// packing, chunk bounds and the twin in models/spectra.py): the east and north
+// parts of the gradient of up to two band-limited fields, a launch over (cell
+// batches of 128) x (chunks of the orders 1 .. L) and a fold where there are several.
+typedef struct GradSynthDesc {
+  const double* K;        // packed [k_rows][16]: row of (m >= 1, l >= m) = (m-1)(L+1) - (m-1) m / 2 + l - m
+  const int* idx;         // [cells] position of each cell inside a plane of out, all < idx_limit
+  const double* cell;     // [cells][4] mu, cos phi, lambda, w (32-byte aligned)
+  const double* a;        // [L+1][L+1] recurrence factors, transposed: a[m][l] (0 where l <= m)
+  const double* b;        // [L+1][L+1] likewise b[m][l]
+  const double* c;        // [L+1] sectoral factors: Q_mm = c[m] cos^(m-1) phi
+  const int* bounds;      // host: [chunks + 1] first order of each chunk, 1 = b[0] < ... < b[chunks] = L + 1
+  const int* bounds_dev;  // the same numbers in device memory
+  double* rec;            // [chunks][2 C][cells] workgroup records (unused, nullable, with one chunk)
+  double* out;            // [C][2][cells]: east, north of every channel, float64
+  long long k_rows;       // L (L+1) / 2
+  long long rec_elems;    // elements rec holds, >= chunks 2 C cells
+  double inv_radius;      // 1 / R, finite and positive
+  int cells;              // cells of the rank
+  int idx_limit;          // what the host checked idx against: must equal cells
+  int C;                  // channels, 1 .. 2
+  int lmax;               // L, 1 .. 1023
+  int chunks;             // order chunks (grid y), 1 .. L
+  int pad_;
+} GradSynthDesc;
+int stsp_grad_synth_launch(const GradSynthDesc* d, hipStream_t stream);
+int stsp_grad_synth_desc_size(void);
 // Point sampling and Lagrangian particles (points_kernel.hip, ops/points.py;
 // definitions and the twin in models/points.py): one thread per point locates
 // it on the dual mesh of the cell centres and gathers four source cells.

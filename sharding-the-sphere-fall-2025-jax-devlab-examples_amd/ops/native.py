@@ -153,9 +153,24 @@ class SynthDesc(ctypes.Structure):
     ]
 
 
+class GradSynthDesc(ctypes.Structure):
+    """Mirror of GradSynthDesc (stsp_kernels.h): gradient synthesis (winds)."""
+    _fields_ = [
+        ("K", ctypes.c_void_p), ("idx", ctypes.c_void_p), ("cell", ctypes.c_void_p),
+        ("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("c", ctypes.c_void_p),
+        ("bounds", ctypes.c_void_p), ("bounds_dev", ctypes.c_void_p),
+        ("rec", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("k_rows", ctypes.c_longlong), ("rec_elems", ctypes.c_longlong), ("inv_radius", ctypes.c_double),
+        ("cells", ctypes.c_int), ("idx_limit", ctypes.c_int), ("C", ctypes.c_int), ("lmax", ctypes.c_int),
+        ("chunks", ctypes.c_int), ("pad_", ctypes.c_int),
+    ]
+
+
 _VP, _CI, _P = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER
 # (launch symbol, its argtypes, descriptor class, size query: (symbol, arguments)) of every
 # descriptor: ``load`` declares both symbols and compares the library's size with the mirror's
+# (tests/test_diagnostics.py pins the classes of this table; the gradient synthesis' descriptor is
+# GRAD_DESCRIPTOR below, declared and compared by ``load`` in the same way)
 DESCRIPTORS = [
     ("stsp_stage_launch", [_CI, _CI, _CI, _CI, _P(StageDesc), _VP], StageDesc, ("stsp_desc_size", (0,))),
     ("stsp_fused_launch", [_CI, _P(FusedDesc), _VP], FusedDesc, ("stsp_desc_size", (1,))),
@@ -166,6 +181,9 @@ DESCRIPTORS = [
     ("stsp_spectra_launch", [_CI, _P(SpectraDesc), _VP], SpectraDesc, ("stsp_spectra_desc_size", ())),
     ("stsp_synth_launch", [_P(SynthDesc), _VP], SynthDesc, ("stsp_synth_desc_size", ())),
 ]
+
+
+GRAD_DESCRIPTOR = ("stsp_grad_synth_launch", [_P(GradSynthDesc), _VP], GradSynthDesc, ("stsp_grad_synth_desc_size", ()))
 
 
 def lib_path() -> str:
@@ -204,7 +222,7 @@ def load(build_if_missing: bool = True):
         L.stsp_fused_record_words.restype = ci
         L.stsp_fused_prime_launch.argtypes = [ci, vp, ci, vp, vp, ci, vp, ci, ci, vp]
         L.stsp_fused_prime_launch.restype = ci
-        for launch, argtypes, cls, (query, args) in DESCRIPTORS:
+        for launch, argtypes, cls, (query, args) in DESCRIPTORS + [GRAD_DESCRIPTOR]:
             fn, size = getattr(L, launch), getattr(L, query)
             fn.argtypes, fn.restype = argtypes, ci
             size.argtypes, size.restype = [ci] * len(args), ci

@@ -21,6 +21,11 @@ Synthesis:  ``synthesise(coeffs)`` is the band-limited field [C, T, n, n] float6
             chunks), and a fold of the chunks where there are several; the twin
             (``models.spectra.synthesise``) otherwise.  Every rank synthesises
             its own cells from the same coefficients.
+Gradient:   ``gradient(coeffs)`` is the east and north part [C, 2, T, n, n] of the
+            gradient of those fields (what k x grad psi and grad chi are made
+            of): ``ops/csrc/grad_synth_kernel.hip`` over (cell batches) x (chunks
+            of the orders 1 .. L), two channels a launch; the twin
+            (``models.spectra.gradient``) otherwise.
 
 All shape contracts the kernels rely on are checked here, on the host, before
 anything is launched.
@@ -53,6 +58,7 @@ class Spectra:
         self.hip = use_hip(e)
         self._pack_index = None                     # synthesis: (l, m) of the packed rows, on the device
         self._abT = None                            # synthesis: the factors a, b as [m][l]
+        self._grad_tables = None                    # gradient synthesis: models.spectra.grad_pack_tables
         self._bounds = {}                           # synthesis: chunks -> (host int array, device int32 tensor)
         # ---- host-side shape contract checks ------------------------------------
         t = self.tab
@@ -182,6 +188,78 @@ class Spectra:
         d.cells, d.idx_limit, d.C, d.lmax, d.chunks = self.cells, self.cells, C, L, chunks
         native.check(self.lib.stsp_synth_launch(d, native.current_stream_handle(e.device)), "synthesis kernel")
         return out.reshape(C, plan.T, plan.n, plan.n)
+
+    # ---- gradient synthesis: coefficients [C, 2, L+1, L+1] to (east, north) [C, 2, T, n, n] ---
+    def default_grad_chunks(self) -> int:
+        """Order chunks of the gradient launch: the fewest that make the grid
+        (cell batches x chunks) at least twice the compute units, at most L."""
+        if not self.hip:
+            return 1
+        nbatch = -(-self.cells // BATCH)
+        return max(1, min(self.lmax, -(-2 * self._cus // nbatch)))
+
+    def gradient(self, coeffs: torch.Tensor, chunks: Optional[int] = None) -> torch.Tensor:
+        """[C, 2, T, n, n] float64 on the engine's device: the horizontal gradient
+        (index 0 east, 1 north; per metre) of the band-limited fields of
+        ``coeffs`` [C, 2, L+1, L+1] float64 at this rank's cell centres, any
+        C >= 1: ``ops/csrc/grad_synth_kernel.hip`` takes two channels a launch.
+        Entries with m > l and S_l0 are not read.  ``chunks``: the kernel's
+        order chunks over the orders 1 .. L (default: ``default_grad_chunks()``);
+        the twin ignores all but its range."""
+        e, t, L = self.e, self.tab, self.lmax
+        if not isinstance(coeffs, torch.Tensor) or coeffs.dim() != 4 or coeffs.shape[1] != 2 \
+                or coeffs.shape[2] != coeffs.shape[3]:
+            raise ValueError(f"gradient: coefficients [C, 2, L+1, L+1] expected, not "
+                             f"{tuple(getattr(coeffs, 'shape', ()))}")
+        if coeffs.dtype != torch.float64:
+            raise ValueError(f"gradient: float64 coefficients expected, not {coeffs.dtype}")
+        C = coeffs.shape[0]
+        if C < 1:
+            raise ValueError(f"gradient: at least one channel expected, not {C}")
+        if coeffs.shape[2] != L + 1:
+            raise ValueError(f"gradient: coefficients to degree {coeffs.shape[2] - 1}, this object's lmax is {L}")
+        if chunks is None:
+            chunks = self.default_grad_chunks()
+        bounds = ms.grad_chunk_bounds(L, chunks)       # ValueError outside 1 .. max(L, 1)
+        plan = e.plan
+        shape = (C, 2, plan.T, plan.n, plan.n)
+        coeffs = coeffs.to(e.device)
+        radius = float(e.geo.grid.radius)
+        if L == 0:
+            return torch.zeros(shape, dtype=torch.float64, device=e.device)
+        if not self.hip:
+            return ms.gradient(coeffs, t, radius).reshape(shape)
+        from . import native
+        if self._grad_tables is None:
+            self._grad_tables = ms.grad_pack_tables(L, e.device)
+        if self._abT is None:
+            self._abT = (t.a.T.contiguous(), t.b.T.contiguous())
+        key = ("grad", chunks)
+        if key not in self._bounds:
+            host = (ctypes.c_int * (chunks + 1))(*bounds)
+            self._bounds[key] = (host, torch.tensor(bounds, dtype=torch.int32, device=e.device))
+        host, dev = self._bounds[key]
+        assert host[0] == 1 and host[chunks] == L + 1 and all(host[k] < host[k + 1] for k in range(chunks))
+        out = torch.empty((C, 2, self.cells), dtype=torch.float64, device=e.device)
+        for k in range(0, C, ms.GRAD_CHANNELS):
+            part = out[k:k + ms.GRAD_CHANNELS]
+            Ck = part.shape[0]
+            K = ms.pack_gradient(coeffs[k:k + Ck], self._grad_tables)
+            assert K.shape == (ms.grad_rows(L), 16) and K.is_contiguous() and part.is_contiguous()
+            rec = None
+            if chunks > 1:
+                rec = torch.empty((chunks, 2 * Ck, self.cells), dtype=torch.float64, device=e.device)
+            d = native.GradSynthDesc()
+            d.K, d.idx, d.cell = native.ptr(K), native.ptr(self.unp), native.ptr(t.cell)
+            d.a, d.b, d.c = native.ptr(self._abT[0]), native.ptr(self._abT[1]), native.ptr(t.c)
+            d.bounds, d.bounds_dev = ctypes.addressof(host), native.ptr(dev)
+            d.rec, d.out = (native.ptr(rec) if rec is not None else None), native.ptr(part)
+            d.k_rows, d.rec_elems = K.shape[0], (rec.numel() if rec is not None else 0)
+            d.inv_radius = 1.0 / radius
+            d.cells, d.idx_limit, d.C, d.lmax, d.chunks = self.cells, self.cells, Ck, L, chunks
+            native.check(self.lib.stsp_grad_synth_launch(d, native.current_stream_handle(e.device)),
+                         "gradient synthesis kernel")
+        return out.reshape(shape)
 
     @staticmethod
     def power(coeffs: torch.Tensor) -> torch.Tensor:

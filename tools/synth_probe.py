@@ -16,6 +16,7 @@ multiply-add rate.
 
     python tools/synth_probe.py                       # C96 t=2 lmax 95, C720 t=2 lmax 255
     python tools/synth_probe.py --sizes 96x2:95 --twin-reps 0 --chunks 1,2,4
+    python tools/synth_probe.py --gradient            # + a row per size: the winds' gradient synthesis
 """
 import argparse
 import json
@@ -44,8 +45,57 @@ def timed(fn, reps, warm):
     return ts
 
 
+def gradient_row(a, hip, sp, N, t, L, fma7):
+    """The gradient synthesis of psi and chi (``Spectra.gradient``, the launches of
+    ops/csrc/grad_synth_kernel.hip with its packing) interleaved, round by round,
+    with the scalar synthesis of seven channels of the same shape: the two launch
+    the same number of matrix instructions (16 columns; the gradient walks the
+    orders 1 .. L).  ``fma7``: the scalar synthesis' multiply-adds."""
+    import torch
+    from stsphere.models import spectra as ms
+    c = sp.partial_tiles(hip.derived()[0][:2])
+    pc = torch.stack(ms.helmholtz(c[0], c[1], hip.grid.radius))
+    seven = torch.cat([sp.partial_fields(), sp.partial_tiles(hip.derived()[0])])
+    gr, sy = [], []
+    for k in range(a.reps):
+        w = a.warm if k == 0 else 0
+        gr += timed(lambda: sp.gradient(pc), 1, w)
+        sy += timed(lambda: sp.synthesise(seven), 1, w)
+    pk = timed(lambda: ms.pack_gradient(pc, sp._grad_tables), a.reps, a.warm)
+    cells = 6 * N * N
+    fma = cells * ms.grad_rows(L) * 16
+    rec = {"row": "gradient", "N": N, "tiles_per_edge": t, "lmax": L, "cells": cells, "channels": 2, "reps": a.reps,
+           "chunks": sp.default_grad_chunks(), "bounds": ms.grad_chunk_bounds(L, sp.default_grad_chunks()),
+           "grad_us_median": statistics.median(gr), "grad_us_min": min(gr), "pack_us_median": statistics.median(pk),
+           "synth7_us_median": statistics.median(sy), "synth7_us_min": min(sy), "synth7_chunks": sp.default_chunks(),
+           "grad_over_synth7": statistics.median(gr) / statistics.median(sy),
+           "matrix_fma": fma, "synth7_matrix_fma": fma7,
+           "grad_matrix_flops_per_s": 2.0 * fma / (statistics.median(gr) * 1e-6)}
+    if a.twin_reps:
+        need = 4 * (L + 1) * cells * 8                   # Q, the shifted rows and D of one order, and the products
+        free = torch.cuda.mem_get_info()[0]
+        if need > free:
+            rec.update(twin_skipped=f"the twin needs about {need / 2 ** 30:.1f} GiB, {free / 2 ** 30:.1f} GiB are free")
+        else:
+            w, ref = [], None
+            for _ in range(a.twin_reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                ref = ms.gradient(pc, sp.tab, hip.grid.radius)
+                e1.record()
+                e1.synchronize()
+                w.append(e0.elapsed_time(e1) * 1e3)
+            got = sp.gradient(pc).reshape(2, -1)
+            ref = ref.reshape(2, -1)
+            rec.update(twin_us_median=statistics.median(w), twin_over_grad=statistics.median(w) / statistics.median(gr),
+                       max_diff_vs_twin=float(((got - ref).abs().amax(1) / ref.abs().amax(1)).max()))
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gradient", action="store_true",
+                    help="also a row for the gradient synthesis of psi and chi against the synthesis of seven channels")
     ap.add_argument("--sizes", default="96x2:95,720x2:255",
                     help="comma list of NxT:LMAX (cells per panel edge x tiles per edge : largest degree)")
     ap.add_argument("--reps", type=int, default=10)
@@ -112,6 +162,8 @@ def main():
                            twin_over_synth=statistics.median(w) / statistics.median(sy),
                            max_diff_vs_twin=float(((got - ref).abs().amax(1) / ref.abs().amax(1)).max()))
         print(json.dumps(rec), flush=True)
+        if a.gradient:
+            print(json.dumps(gradient_row(a, hip, sp, N, t, L, fma)), flush=True)
         del hip, sp
         torch.cuda.empty_cache()
 
