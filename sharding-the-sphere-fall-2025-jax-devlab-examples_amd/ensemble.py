@@ -128,6 +128,7 @@ class Ensemble:
         self.steps_per_graph = steps_per_graph
         self._graph = None
         self._stats = None
+        self._letkf = None
         phys0 = physics_factory()
         if getattr(phys0, "time_dependent", False):
             raise ValueError(f"an ensemble of a time-dependent physics ({phys0.name}, flow "
@@ -381,6 +382,67 @@ class Ensemble:
         from .models.ensemble_stats import ensemble_stats
         x = torch.stack([e.tiles_view()[field] for e in self.engines])      # [M, T, n, n]
         return ensemble_stats(x, e0.tens["area"].reshape(x.shape[1:]))
+
+    # ---- data assimilation ------------------------------------------------------
+    def _sample_members(self, p: torch.Tensor, fields: torch.Tensor) -> torch.Tensor:
+        """Y [M, K] float64: field ``fields[k]`` of every member at ``p[k]``
+        (member 0's sampler on each member's padded state)."""
+        s = self.engines[0].points()
+        k = torch.arange(p.shape[0], device=p.device)
+        return torch.stack([s.fields(p, e.state)[fields, k] for e in self.engines]).contiguous()
+
+    def assimilate(self, points, values, sigma, fields=0, localisation: Optional[float] = None,
+                   inflation: float = 1.0) -> dict:
+        """One LETKF analysis of the members (models/letkf.py) from K
+        observations: ``points`` [K, 3] unit vectors, ``values`` [K], ``sigma``
+        (scalar or [K], > 0), ``fields`` (one state field index or one per
+        observation), ``localisation`` (Gaspari-Cohn length in metres; None: the
+        global ETKF) and the multiplicative ``inflation`` >= 1.  Returns
+        ``analysis`` [M, F, T, n, n] (a view of the members' states),
+        ``rms_before`` / ``rms_after`` (RMS of (y - ybar) / sigma before and
+        after, the latter from a second sampling pass) and ``nobs_max`` (the
+        most observations any cell saw).  Batched mode on the HIP backend runs
+        ops/csrc/letkf_kernel.hip in place on the batched state (the captured
+        graph holds the same buffers and stays valid); every other setting
+        stacks the members, runs the twin and writes back with ``set_state``.
+        Legal between ``run()`` calls.  The analysis does not conserve mass and
+        does not keep h positive (check ``h.min()``)."""
+        from .models import letkf as ml
+        e0 = self.engines[0]
+        p, y, sg, fl = ml.check_args(self.members, e0.physics.F, points, values, sigma, fields, localisation, inflation)
+        dev = e0.device
+        p, y, sg, fl = p.to(dev).contiguous(), y.to(dev), sg.to(dev), fl.to(dev)
+        Y = self._sample_members(p, fl)
+        rms_before = ml.innovation_rms(Y, y, sg)
+        if self.mode == "batched" and self.native:
+            if self._letkf is None:
+                from .ops.letkf import Letkf
+                self._letkf = Letkf(e0, self.members)
+            nmax = self._letkf.analyse(self.batch[0], Y, p, y, sg, localisation, float(inflation))
+        else:
+            X = self.states()
+            ctr = torch.as_tensor(e0.geo.center, dtype=torch.float64, device=dev).reshape(-1, 3)
+            Xa, nmax = ml.analysis(X.reshape(self.members, e0.physics.F, -1), Y, y, sg, ctr, p, float(self.grid.radius),
+                                   localisation, float(inflation))
+            for m, e in enumerate(self.engines):
+                e.set_state(Xa[m].reshape(X.shape[1:]).to(e.dtype))
+        rms_after = ml.innovation_rms(self._sample_members(p, fl), y, sg)
+        return {"analysis": self.states(), "rms_before": rms_before, "rms_after": rms_after, "nobs_max": int(nmax)}
+
+    def observe(self, truth_engine: Engine, points, sigma, fields=0, seed: int = 0) -> torch.Tensor:
+        """Synthetic observations [K] float64 (on the truth engine's device) for
+        the identical-twin experiment: ``truth_engine``'s state sampled at
+        ``points`` [K, 3] (field ``fields``: one index or one per point) plus
+        N(0, sigma^2) noise from a fixed-seed generator."""
+        from .models import letkf as ml
+        K = len(points)
+        p, _, sg, fl = ml.check_args(ml.MIN_M, truth_engine.physics.F, points, np.zeros(K), sigma,
+                                     fields, None, 1.0)
+        dev = truth_engine.device
+        p = p.to(dev).contiguous()
+        val = truth_engine.points().fields(p)[fl.to(dev), torch.arange(K, device=dev)]
+        noise = torch.randn(K, generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float64)
+        return val + (sg * noise).to(dev)
 
     def global_fields(self, field: int = 0) -> np.ndarray:
         """[M, 6, N, N] global field of every member (host)."""

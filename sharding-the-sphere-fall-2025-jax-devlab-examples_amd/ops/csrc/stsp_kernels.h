@@ -506,6 +506,40 @@ typedef struct EnsStatsDesc {
 } EnsStatsDesc;
 int stsp_ensemble_stats_launch(int dtype, const EnsStatsDesc* d, hipStream_t stream);
 int stsp_ensemble_stats_desc_size(void);
+// LETKF analysis of a batched state in place (letkf_kernel.hip, ops/letkf.py;
+// definitions and the twin in models/letkf.py): a preparation launch (ybar, the
+// obs-major perturbations Yp and the innovations d from Y), then one workgroup
+// per 8 x 8 cell block (ragged): observation compaction by ballot, the weighted
+// Gram matrix on the fp64 matrix cores, in-wave Jacobi, transform and store.
+// Everything but Q is float64.  err[0] is set to 1 when a cell's Jacobi reaches
+// its sweep cap; the caller clears it before and reads it after the launch.
+#define STSP_LETKF_MIN_M 2
+#define STSP_LETKF_MAX_M 32
+#define STSP_LETKF_MAX_K 65535
+typedef struct LetkfDesc {
+  void* Q;              // [M][F][S] batched state (element type), padded layout; interior cells are read and written
+  const double* Y;      // [M][K] the members in observation space
+  const double* yv;     // [K] observed values
+  const double* p;      // [K][3] observation points (unit vectors)
+  const double* sigma;  // [K] observation error standard deviations, > 0
+  const double* centers;  // [T][n][n][3] cell centres (unit vectors)
+  double* Yp;           // [K][Mpad] work: Y - ybar, zero in the padded columns
+  double* d;            // [K] work: yv - ybar
+  int* nobs;            // [nblocks] out: the most observations (w > 0) a cell of the block saw
+  int* err;             // [1] the error word
+  long long member_stride;  // elements between members, >= F * S
+  int M, Mpad;          // members 2 .. 32; Mpad = 16 (M <= 16) or 32
+  int F, K;             // fields per member; observations 1 .. 65535
+  int ntile, n, S, mg, pw;  // as StageDesc
+  int nblocks;          // ntile * ceil(n / 8)^2
+  int localised;        // 0: every weight is 1 / sigma^2 (global ETKF); 1: Gaspari-Cohn with length Lc
+  int pad_;
+  double radius;        // sphere radius (m)
+  double Lc;            // localisation length (m), read when localised
+  double rho;           // multiplicative inflation >= 1
+} LetkfDesc;
+int stsp_letkf_launch(int dtype, const LetkfDesc* d, hipStream_t stream);
+int stsp_letkf_desc_size(void);
 // Time-dependent winds of the advection model (wind_kernel.hip, ops/wind.py; the
 // twin: models/advection.py): one launch before a Runge-Kutta stage refills the
 // stage kernel's transport tables ex / ey in place at the stage time
