@@ -27,6 +27,9 @@
                                                        the streamfunction / velocity_potential of a
                                                        shallow-water history, or its rotational_wind /
                                                        divergent_wind (arrays u, v), on the CPU
+    ingest CONFIG.yaml DATA.npz OUT.zarr               ingest the lat-lon arrays of DATA.npz (lat, lon, h, u, v, ..;
+                                                       Solver.set_from_latlon) over the config's initial state
+                                                       and write it as an io.initial_condition group
     ensemble CONFIG.yaml [--members M] [--amplitude A] [--days D | --nsteps K] [--batched]
                                                        perturbed members of one config on one device
                                                        (--batched: every member's stage in one launch)
@@ -91,6 +94,10 @@ def main(argv=None):
     sy.add_argument("out")
     sy.add_argument("--band", type=int, nargs=2, metavar=("LMIN", "LCUT"), default=None,
                     help="keep the degrees LMIN .. LCUT only")
+    ig = sub.add_parser("ingest")
+    ig.add_argument("config")
+    ig.add_argument("data")
+    ig.add_argument("out")
     en = sub.add_parser("ensemble")
     en.add_argument("config")
     en.add_argument("--members", type=int, default=2)
@@ -172,6 +179,9 @@ def main(argv=None):
         r = regrid_history(a.history, a.field, a.nlat, a.nlon)
         np.savez(a.out, **r)
         print(json.dumps({"out": a.out, "field": a.field, "shape": list(r["field"].shape)}))
+        return 0
+    if a.cmd == "ingest":
+        print(json.dumps(ingest_latlon(a.config, a.data, a.out)))
         return 0
     if a.cmd == "ensemble":
         print(json.dumps(run_ensemble(a.config, a.members, a.amplitude, a.days, a.nsteps, batched=a.batched),
@@ -292,6 +302,23 @@ def regrid_history(history: str, field: str, nlat: int, nlon: int) -> dict:
     out = torch.stack(out)
     return {"field": out.numpy(), "zonal_mean": ml.zonal_mean(out).numpy(), "lat": lat, "lon": lon,
             "time": zarr_lite.read_array(history, "time")}
+
+
+def ingest_latlon(config, data: str, out: str) -> dict:
+    """The config's initial state with the lat-lon arrays of ``data`` (.npz, as
+    ``io.initial_latlon``) ingested over it, written to ``out`` as the zarr group
+    ``io.initial_condition`` reads (same attributes; physics and case of the config)."""
+    from .driver import Solver
+    from .utils.config import load_config
+    c = load_config(config)
+    if os.path.exists(os.path.join(out, ".zgroup")):
+        raise ValueError(f"{out}: exists already (an existing group would be read, not written)")
+    c.io.initial_condition, c.io.restore, c.io.initial_latlon = None, None, data
+    s = Solver(c, verbose=False)
+    s.initialize()
+    s._initial_condition_stage(out)
+    s.close()
+    return {"out": out, "fields": list(s.fields), "N": s.layout.N}
 
 
 def spectrum_history(history: str, field: str, lmax: int) -> dict:

@@ -449,8 +449,12 @@ class Solver(SolverDiagnostics):
         if self._ispec is not None:
             self._log(f"Implicit diffusion: theta = {self._ispec['theta']:g}, one BiCGStab Helmholtz solve per step "
                       f"(tol {self._ispec['tol']:g}); time.integrator is ignored")
+        if c.io.initial_condition and c.io.initial_latlon:
+            raise ValueError("io.initial_condition and io.initial_latlon: give one of the two")
         if c.io.initial_condition and not c.io.restore:
             self._initial_condition_stage(c.io.initial_condition)
+        if c.io.initial_latlon and not c.io.restore:
+            self._initial_latlon_stage(c.io.initial_latlon)
         if c.io.restore:
             path = c.io.restore
             if path == "latest":
@@ -510,6 +514,40 @@ class Solver(SolverDiagnostics):
                 zarr_lite.write_array(path, f, g[k], chunks=(1, self.layout.N, self.layout.N))
             self._log(f"Initial conditions: wrote {path}")
         self._barrier()
+
+    def set_from_latlon(self, lat, lon, order: int = 3, quadrature: int = 1, **arrays) -> None:
+        """Overwrite prognostic fields of every engine, in place, from arrays
+        [nlat, nlon] (numpy or torch) on the lat-lon grid ``lat`` / ``lon``
+        (radians; uniform, full circle, with both poles or cell-centred:
+        models/latlon_in.py).  ``arrays`` are named by field: ``h`` (the layer
+        depth), ``u`` and ``v`` (east / north wind, m/s, together), ``q0`` .. (mixing
+        ratios) for shallow water; ``q`` / ``T`` for the advection / diffusion model.
+        Only the named fields change.  Winds without ``h`` keep the current h:
+        M = h_current V_t; likewise tracers without ``h``.  ``order`` 1 (bilinear) or
+        3 (cubic Lagrange); ``quadrature`` 1, 2 or 4 Gauss points per cell edge (1:
+        the value at the cell centre).  On the device the kernel of
+        ops/csrc/latlon_in_kernel.hip runs; with ``backend: torch`` or on the CPU the
+        twin.  The topography stays the case's; a free-surface height, non-uniform
+        latitudes, regional grids and layered runs are refused or out of scope."""
+        if not self.engines:
+            self.initialize()
+        if self.mode == "spmd":
+            raise ValueError("lat-lon input: one process per rank (spmd) is not supported (the step runner's exchange "
+                             "is primed from the state it was built with); run one rank or virtual ranks in one process")
+        for e in self.engines:
+            e.set_from_latlon(lat, lon, order=order, quadrature=quadrature, **arrays)
+
+    def _initial_latlon_stage(self, path: str) -> None:
+        """``io.initial_latlon``: an .npz of ``lat``, ``lon``, arrays by field name
+        and optionally ``order`` and ``quadrature``, ingested over the analytic state."""
+        with np.load(path) as z:
+            d = {k: z[k] for k in z.files}
+        for k in ("lat", "lon"):
+            if k not in d:
+                raise ValueError(f"{path}: io.initial_latlon needs the arrays lat and lon")
+        kw = {k: int(d.pop(k)) for k in ("order", "quadrature") if k in d}
+        self.set_from_latlon(d.pop("lat"), d.pop("lon"), **kw, **d)
+        self._log(f"Initial conditions: ingested {sorted(d)} from {path}")
 
     # ---- state access ---------------------------------------------------------
     @property

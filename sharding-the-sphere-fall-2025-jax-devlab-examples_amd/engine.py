@@ -325,6 +325,24 @@ class Engine:
             self._latlon[key] = LatLon(self, lat, lon)
         return self._latlon[key]
 
+    def latlon_in(self, lat, lon):
+        """``ops.latlon_in.LatLonIn`` of this engine for the source grid ``lat`` /
+        ``lon`` (radians), built on first use and cached per grid."""
+        from .ops.latlon_in import LatLonIn
+        lat = np.ascontiguousarray(lat, dtype=np.float64)
+        lon = np.ascontiguousarray(lon, dtype=np.float64)
+        key = ("in", lat.tobytes(), lon.tobytes())
+        if key not in self._latlon:
+            self._latlon[key] = LatLonIn(self, lat, lon)
+        return self._latlon[key]
+
+    def set_from_latlon(self, lat, lon, order: int = 3, quadrature: int = 1, **arrays) -> None:
+        """Overwrite the named fields of this rank's state from arrays on the
+        lat-lon grid ``lat`` / ``lon`` (``Solver.set_from_latlon``)."""
+        self.latlon_in(lat, lon).ingest(arrays, order, quadrature)
+        if self.clock is not None:
+            self.clock.set(self._step_count)
+
     def points(self):
         """``ops.points.PointSampler`` of this engine, built on first use."""
         if getattr(self, "_points", None) is None:

@@ -429,6 +429,19 @@ class Ensemble:
         rms_after = ml.innovation_rms(self._sample_members(p, fl), y, sg)
         return {"analysis": self.states(), "rms_before": rms_before, "rms_after": rms_after, "nobs_max": int(nmax)}
 
+    def set_from_latlon(self, lat, lon, order: int = 3, quadrature: int = 1, members=None, **arrays) -> None:
+        """``Solver.set_from_latlon`` for the chosen ``members`` (default: all):
+        their named fields are overwritten in place from the lat-lon arrays, the
+        same values for each (the members' perturbations are not reapplied).  In
+        batched mode the members' states are slices of ``batch[0]``, so the captured
+        graph stays valid.  Legal between ``run()`` calls."""
+        ms = range(self.members) if members is None else [int(m) for m in members]
+        for m in ms:
+            if not 0 <= m < self.members:
+                raise ValueError(f"members: {m} is not one of the {self.members} members")
+        for m in ms:
+            self.engines[m].set_from_latlon(lat, lon, order=order, quadrature=quadrature, **arrays)
+
     def observe(self, truth_engine: Engine, points, sigma, fields=0, seed: int = 0) -> torch.Tensor:
         """Synthetic observations [K] float64 (on the truth engine's device) for
         the identical-twin experiment: ``truth_engine``'s state sampled at

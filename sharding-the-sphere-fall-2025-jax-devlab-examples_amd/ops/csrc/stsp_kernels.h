@@ -269,6 +269,33 @@ typedef struct LatLonDesc {
 } LatLonDesc;
 int stsp_latlon_launch(int dtype, const LatLonDesc* d, hipStream_t stream);
 int stsp_latlon_desc_size(void);
+// Lat-lon input (latlon_in_kernel.hip, ops/latlon_in.py; definitions and the twin
+// in models/latlon_in.py): a preparation launch (one workgroup per source row:
+// float64 work copy, Cartesian winds, pole rows) and an ingest launch over the
+// rank's cells (q q lanes per cell) that writes the interior of the padded state.
+typedef struct LatLonInDesc {
+  const void* src;      // prepare in: input channels [h?][u, v?][tracers][nlat][nlon], fp32 or fp64 (src_dtype)
+  double* work;         // prepare out / ingest in: [C][nlat][nlon], ordered h?, Vx, Vy, Vz?, tracers
+  void* Q;              // ingest out: padded state [F][S], element type
+  const int* tiles;     // [ntile][3] panel, I0, J0 of the rank's tiles
+  long long S;          // field stride of Q in elements
+  double lat0, dlat, lon0, dlon;   // source node j, i at lat0 + j dlat, lon0 + i dlon (radians)
+  int nlat, nlon;
+  int poles;            // 1 = rows 0 and nlat - 1 are the poles, 0 = cell-centred rows
+  int C;                // work channels = has_h + 3 has_wind + nq  (1 .. 8)
+  int has_h;            // channel 0 goes to field 0 (else the products use the state's field 0)
+  int has_wind;         // M = h V_t goes to fields 1 .. 3
+  int nq;               // tracer channels; channel k goes to field qfield[k] as h q_k
+  int qfield[4];
+  int F;                // fields of Q
+  int ntile, n, N, mg, pw;   // tiles of n x n cells of C<N>, ghost width, padded width n + 2 mg
+  int order;            // 1 bilinear, 3 cubic Lagrange
+  int quad;             // Gauss points per cell edge: 1, 2 or 4
+  int phases;           // bit 0 prepare, bit 1 ingest
+  int src_dtype;        // element type of src: 0 fp32, 1 fp64
+} LatLonInDesc;
+int stsp_latlon_in_launch(int dtype, const LatLonInDesc* d, hipStream_t stream);
+int stsp_latlon_in_desc_size(void);
 // Spherical-harmonic analysis (spectra_kernel.hip, ops/spectra.py; definitions,
 // tables and the twin in models/spectra.py): an analysis launch over (order m) x
 // (cell slabs) that leaves one partial record per workgroup, then a fold of the

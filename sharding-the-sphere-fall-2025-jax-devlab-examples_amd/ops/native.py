@@ -114,6 +114,20 @@ class LatLonDesc(ctypes.Structure):
     ]
 
 
+class LatLonInDesc(ctypes.Structure):
+    """Mirror of LatLonInDesc (stsp_kernels.h): lat-lon input."""
+    _fields_ = [
+        ("src", ctypes.c_void_p), ("work", ctypes.c_void_p), ("Q", ctypes.c_void_p), ("tiles", ctypes.c_void_p),
+        ("S", ctypes.c_longlong),
+        ("lat0", ctypes.c_double), ("dlat", ctypes.c_double), ("lon0", ctypes.c_double), ("dlon", ctypes.c_double),
+        ("nlat", ctypes.c_int), ("nlon", ctypes.c_int), ("poles", ctypes.c_int), ("C", ctypes.c_int),
+        ("has_h", ctypes.c_int), ("has_wind", ctypes.c_int), ("nq", ctypes.c_int), ("qfield", ctypes.c_int * 4),
+        ("F", ctypes.c_int),
+        ("ntile", ctypes.c_int), ("n", ctypes.c_int), ("N", ctypes.c_int), ("mg", ctypes.c_int), ("pw", ctypes.c_int),
+        ("order", ctypes.c_int), ("quad", ctypes.c_int), ("phases", ctypes.c_int), ("src_dtype", ctypes.c_int),
+    ]
+
+
 class PointsDesc(ctypes.Structure):
     """Mirror of PointsDesc (stsp_kernels.h): point sampling and particles."""
     _fields_ = [
@@ -170,7 +184,8 @@ _VP, _CI, _P = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER
 # (launch symbol, its argtypes, descriptor class, size query: (symbol, arguments)) of every
 # descriptor: ``load`` declares both symbols and compares the library's size with the mirror's
 # (tests/test_diagnostics.py pins the classes of this table; the gradient synthesis' descriptor is
-# GRAD_DESCRIPTOR below, declared and compared by ``load`` in the same way)
+# GRAD_DESCRIPTOR below and the lat-lon input's LATLON_IN_DESCRIPTOR, declared and compared by
+# ``load`` in the same way)
 DESCRIPTORS = [
     ("stsp_stage_launch", [_CI, _CI, _CI, _CI, _P(StageDesc), _VP], StageDesc, ("stsp_desc_size", (0,))),
     ("stsp_fused_launch", [_CI, _P(FusedDesc), _VP], FusedDesc, ("stsp_desc_size", (1,))),
@@ -184,6 +199,8 @@ DESCRIPTORS = [
 
 
 GRAD_DESCRIPTOR = ("stsp_grad_synth_launch", [_P(GradSynthDesc), _VP], GradSynthDesc, ("stsp_grad_synth_desc_size", ()))
+LATLON_IN_DESCRIPTOR = ("stsp_latlon_in_launch", [_CI, _P(LatLonInDesc), _VP], LatLonInDesc,
+                        ("stsp_latlon_in_desc_size", ()))
 
 
 def lib_path() -> str:
@@ -222,7 +239,7 @@ def load(build_if_missing: bool = True):
         L.stsp_fused_record_words.restype = ci
         L.stsp_fused_prime_launch.argtypes = [ci, vp, ci, vp, vp, ci, vp, ci, ci, vp]
         L.stsp_fused_prime_launch.restype = ci
-        for launch, argtypes, cls, (query, args) in DESCRIPTORS + [GRAD_DESCRIPTOR]:
+        for launch, argtypes, cls, (query, args) in DESCRIPTORS + [GRAD_DESCRIPTOR, LATLON_IN_DESCRIPTOR]:
             fn, size = getattr(L, launch), getattr(L, query)
             fn.argtypes, fn.restype = argtypes, ci
             size.argtypes, size.restype = [ci] * len(args), ci

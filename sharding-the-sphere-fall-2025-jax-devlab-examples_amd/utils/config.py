@@ -111,6 +111,10 @@ class IOConfig:
     # jax.zarr"): a zarr group written on the first run, read when present
     geometry: Optional[str] = None
     initial_condition: Optional[str] = None
+    # an .npz of lat, lon (radians) and arrays [nlat, nlon] by field name (h, u, v, q0 ..;
+    # optional order, quadrature) ingested over the case's initial state
+    # (models/latlon_in.py; Solver.set_from_latlon); not with initial_condition; null = off
+    initial_latlon: Optional[str] = None
     # [nlat, nlon]: every history frame is also written on the cell-centred
     # lat-lon grid, to history_latlon.zarr (models/latlon.py); null = off
     latlon: Optional[List[int]] = None
