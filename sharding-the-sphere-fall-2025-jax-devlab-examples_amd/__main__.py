@@ -30,6 +30,10 @@
     ingest CONFIG.yaml DATA.npz OUT.zarr               ingest the lat-lon arrays of DATA.npz (lat, lon, h, u, v, ..;
                                                        Solver.set_from_latlon) over the config's initial state
                                                        and write it as an io.initial_condition group
+    resample SRC.zarr FRAME CONFIG.yaml OUT.zarr       transfer frame FRAME of a history (or an io.initial_condition
+                                                       group; FRAME is then ignored) at its own N onto the grid of
+                                                       CONFIG (Solver.set_from_cubed: N ratio 1, 2, 4 or 8 either
+                                                       way) and write it as an io.initial_condition group
     ensemble CONFIG.yaml [--members M] [--amplitude A] [--days D | --nsteps K] [--batched]
                                                        perturbed members of one config on one device
                                                        (--batched: every member's stage in one launch)
@@ -98,6 +102,11 @@ def main(argv=None):
     ig.add_argument("config")
     ig.add_argument("data")
     ig.add_argument("out")
+    rs = sub.add_parser("resample")
+    rs.add_argument("src")
+    rs.add_argument("frame", type=int)
+    rs.add_argument("config")
+    rs.add_argument("out")
     en = sub.add_parser("ensemble")
     en.add_argument("config")
     en.add_argument("--members", type=int, default=2)
@@ -182,6 +191,9 @@ def main(argv=None):
         return 0
     if a.cmd == "ingest":
         print(json.dumps(ingest_latlon(a.config, a.data, a.out)))
+        return 0
+    if a.cmd == "resample":
+        print(json.dumps(resample_state(a.src, a.frame, a.config, a.out)))
         return 0
     if a.cmd == "ensemble":
         print(json.dumps(run_ensemble(a.config, a.members, a.amplitude, a.days, a.nsteps, batched=a.batched),
@@ -319,6 +331,37 @@ def ingest_latlon(config, data: str, out: str) -> dict:
     s._initial_condition_stage(out)
     s.close()
     return {"out": out, "fields": list(s.fields), "N": s.layout.N}
+
+
+def resample_state(src: str, frame: int, config, out: str) -> dict:
+    """Frame ``frame`` of the history ``src`` (or the state of an
+    ``io.initial_condition`` group) transferred from its own N onto the grid of
+    ``config`` (``Solver.set_from_cubed``) and written to ``out`` as the zarr group
+    ``io.initial_condition`` reads."""
+    import numpy as np
+    from .driver import Solver
+    from .utils import zarr_lite
+    from .utils.config import load_config
+    c = load_config(config)
+    if os.path.exists(os.path.join(out, ".zgroup")):
+        raise ValueError(f"{out}: exists already (an existing group would be read, not written)")
+    c.io.initial_condition, c.io.restore, c.io.initial_latlon = None, None, None
+    s = Solver(c, verbose=False)
+    s.initialize()
+    have = set(zarr_lite.list_arrays(src))
+    missing = [f for f in s.fields if f not in have]
+    if missing:
+        raise ValueError(f"{src}: no array(s) {missing}; the run of {config} carries {list(s.fields)}")
+    arrs = [zarr_lite.read_array(src, f) for f in s.fields]
+    if arrs[0].ndim == 4:
+        if not 0 <= frame < arrs[0].shape[0]:
+            raise ValueError(f"{src}: frame {frame} of {arrs[0].shape[0]}")
+        arrs = [a[frame] for a in arrs]
+    state = np.stack(arrs).astype(np.float64)
+    s.set_from_cubed(state)
+    s._initial_condition_stage(out)
+    s.close()
+    return {"out": out, "fields": list(s.fields), "N_source": int(state.shape[-1]), "N": s.layout.N}
 
 
 def spectrum_history(history: str, field: str, lmax: int) -> dict:

@@ -33,7 +33,7 @@ import torch
 from .diagnostics import LATLON_WINDS, SolverDiagnostics
 from .engine import Engine, VirtualCluster
 from .models.advection import Advection
-from .models.base import limiter_code
+from .models.base import interior, limiter_code
 from .models.derived import FIELDS as DERIVED_FIELDS, INVARIANTS
 from .models.diffusion import OPERATORS, ConsistentDiffusion, Diffusion, implicit_spec
 from .models.geometry import DAY, EARTH_RADIUS, CubedSphereGrid
@@ -536,6 +536,52 @@ class Solver(SolverDiagnostics):
                              "is primed from the state it was built with); run one rank or virtual ranks in one process")
         for e in self.engines:
             e.set_from_latlon(lat, lon, order=order, quadrature=quadrature, **arrays)
+
+    def _check_cubed(self, shape, N: int) -> None:
+        from .models.transfer import direction
+        if self.mode == "spmd":
+            raise ValueError("grid transfer: one process per rank (spmd) is not supported (the step runner's exchange "
+                             "is primed from the state it was built with); run one rank or virtual ranks in one process")
+        F = len(self.fields)
+        if len(shape) != 4 or shape[0] != F or shape[1] != 6 or shape[2] != shape[3]:
+            raise ValueError(f"grid transfer: a state [{F}, 6, Ns, Ns] of the fields {self.fields} expected, "
+                             f"not {tuple(shape)}")
+        direction(int(shape[-1]), N)
+
+    def set_from_cubed(self, state, limiter: str = "bj") -> None:
+        """Overwrite every engine's state, in place, from the global state ``state``
+        [F, 6, Ns, Ns] (numpy or torch; F the model's fields) of a cubed-sphere grid
+        with Ns = N / r (refined: least-squares gradient, mean-free child deltas,
+        Barth-Jespersen factor; ``limiter="none"`` switches the factor off), Ns = r N
+        (coarsened: exact area means) or Ns = N, r in 2, 4, 8 (models/transfer.py).
+        Conservative to rounding for h, scalars and tracer masses; momentum is rebuilt
+        from v = M / h and is tangent.  Step count, time and the topography stay.  On
+        the device the kernel of ops/csrc/transfer_kernel.hip runs; with ``backend:
+        torch`` or on the CPU the twin.  Other ratios (chain two calls beyond 8) and
+        one process per rank are refused."""
+        if not self.engines:
+            self.initialize()
+        self._check_cubed(tuple(state.shape), self.layout.N)
+        for e in self.engines:
+            e.set_from_cubed(state, limiter)
+
+    def resampled_state(self, N_target: int, limiter: str = "bj") -> Optional[np.ndarray]:
+        """The present state on C<N_target> as [F, 6, Nt, Nt] float64 on rank 0, by
+        the rules of ``set_from_cubed``; the solver is not changed."""
+        from .ops.transfer import Transfer
+        g = self.gather_global()
+        if g is None:
+            return None
+        self._check_cubed(g.shape, int(N_target))
+        lay = TileLayout(int(N_target), 1, 1, ng=1)
+        e0 = self.engines[0]
+        tr = Transfer(self.physics, lay, 0, CubedSphereGrid(int(N_target), self.grid.radius), torch.float64, self.device,
+                      e0.backend == "hip" and self.device.type == "cuda")
+        plan = lay.plan(0)
+        q = torch.zeros((len(self.fields), plan.S), dtype=torch.float64, device=self.device)
+        tr.apply(g, q, limiter)
+        assert list(plan.tiles) == list(range(6))           # one tile per panel: the tiles are the panels
+        return interior(q, plan.T, plan.n, plan.ng).cpu().numpy().copy()
 
     def _initial_latlon_stage(self, path: str) -> None:
         """``io.initial_latlon``: an .npz of ``lat``, ``lon``, arrays by field name

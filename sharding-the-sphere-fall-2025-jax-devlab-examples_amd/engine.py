@@ -343,6 +343,22 @@ class Engine:
         if self.clock is not None:
             self.clock.set(self._step_count)
 
+    @property
+    def transfer(self):
+        """``ops.transfer.Transfer`` onto this engine's grid, built on first use."""
+        if getattr(self, "_transfer", None) is None:
+            from .ops.transfer import Transfer
+            self._transfer = Transfer.of_engine(self)
+        return self._transfer
+
+    def set_from_cubed(self, state, limiter: str = "bj") -> None:
+        """Overwrite this rank's state in place from the global state [F, 6, Ns, Ns]
+        of another (or the same) resolution (``Solver.set_from_cubed``)."""
+        self.transfer.apply(state, self.pool[0], limiter)
+        self.refresh_halos(self.pool[0])
+        if self.clock is not None:
+            self.clock.set(self._step_count)
+
     def points(self):
         """``ops.points.PointSampler`` of this engine, built on first use."""
         if getattr(self, "_points", None) is None:

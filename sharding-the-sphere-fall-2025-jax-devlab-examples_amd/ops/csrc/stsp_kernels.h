@@ -296,6 +296,29 @@ typedef struct LatLonInDesc {
 } LatLonInDesc;
 int stsp_latlon_in_launch(int dtype, const LatLonInDesc* d, hipStream_t stream);
 int stsp_latlon_in_desc_size(void);
+// Grid transfer C_Ns -> C_N (transfer_kernel.hip, ops/transfer.py; definitions and
+// the twin in models/transfer.py): one launch that refines (N = r Ns) or coarsens
+// (Ns = r N) the global unpadded source into the rank's padded state.
+typedef struct TransferDesc {
+  const double* src;     // [F][6 Ns Ns] global source, float64
+  void* Q;               // out: padded state [F][S], element type
+  const int* padmap;     // [6 N N] index of every target cell in Q's rows; -1: not this rank's
+  const int* nbr;        // refine: [6 Ns Ns][4] global source cell across W, E, S, N
+  const double* W;       // refine: [12][6 Ns Ns] gradient weights, row 3 k + c: neighbour k, component c
+  const double* ctr_s;   // [3][6 Ns Ns] unit centres of the source grid
+  const double* area_s;  // [Ns Ns] exact areas of the source grid (one panel)
+  const double* ctr_t;   // [3][6 N N] unit centres of the target grid
+  const double* area_t;  // [N N]
+  long long S;           // field stride of Q in elements
+  int Ns, N, r;
+  int coarsen;           // 0 refine, 1 coarsen
+  int F;                 // rows of src and Q (1 .. 32)
+  int limiter;           // refine: 1 Barth-Jespersen, 0 none
+  int kind[32];          // 0 scalar, 1 momentum row (in triples), 2 tracer mass
+  int depth[32];         // kinds 1, 2: the row of h
+} TransferDesc;
+int stsp_transfer_launch(int dtype, const TransferDesc* d, hipStream_t stream);
+int stsp_transfer_desc_size(void);
 // Spherical-harmonic analysis (spectra_kernel.hip, ops/spectra.py; definitions,
 // tables and the twin in models/spectra.py): an analysis launch over (order m) x
 // (cell slabs) that leaves one partial record per workgroup, then a fold of the

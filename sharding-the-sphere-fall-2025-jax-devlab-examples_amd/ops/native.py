@@ -128,6 +128,17 @@ class LatLonInDesc(ctypes.Structure):
     ]
 
 
+class TransferDesc(ctypes.Structure):
+    """Mirror of TransferDesc (stsp_kernels.h): grid transfer between C_N grids."""
+    _fields_ = [
+        ("src", ctypes.c_void_p), ("Q", ctypes.c_void_p), ("padmap", ctypes.c_void_p), ("nbr", ctypes.c_void_p),
+        ("W", ctypes.c_void_p), ("ctr_s", ctypes.c_void_p), ("area_s", ctypes.c_void_p), ("ctr_t", ctypes.c_void_p),
+        ("area_t", ctypes.c_void_p), ("S", ctypes.c_longlong),
+        ("Ns", ctypes.c_int), ("N", ctypes.c_int), ("r", ctypes.c_int), ("coarsen", ctypes.c_int),
+        ("F", ctypes.c_int), ("limiter", ctypes.c_int), ("kind", ctypes.c_int * 32), ("depth", ctypes.c_int * 32),
+    ]
+
+
 class PointsDesc(ctypes.Structure):
     """Mirror of PointsDesc (stsp_kernels.h): point sampling and particles."""
     _fields_ = [
@@ -184,8 +195,8 @@ _VP, _CI, _P = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER
 # (launch symbol, its argtypes, descriptor class, size query: (symbol, arguments)) of every
 # descriptor: ``load`` declares both symbols and compares the library's size with the mirror's
 # (tests/test_diagnostics.py pins the classes of this table; the gradient synthesis' descriptor is
-# GRAD_DESCRIPTOR below and the lat-lon input's LATLON_IN_DESCRIPTOR, declared and compared by
-# ``load`` in the same way)
+# GRAD_DESCRIPTOR below, the lat-lon input's LATLON_IN_DESCRIPTOR and the grid transfer's
+# TRANSFER_DESCRIPTOR, declared and compared by ``load`` in the same way)
 DESCRIPTORS = [
     ("stsp_stage_launch", [_CI, _CI, _CI, _CI, _P(StageDesc), _VP], StageDesc, ("stsp_desc_size", (0,))),
     ("stsp_fused_launch", [_CI, _P(FusedDesc), _VP], FusedDesc, ("stsp_desc_size", (1,))),
@@ -201,6 +212,8 @@ DESCRIPTORS = [
 GRAD_DESCRIPTOR = ("stsp_grad_synth_launch", [_P(GradSynthDesc), _VP], GradSynthDesc, ("stsp_grad_synth_desc_size", ()))
 LATLON_IN_DESCRIPTOR = ("stsp_latlon_in_launch", [_CI, _P(LatLonInDesc), _VP], LatLonInDesc,
                         ("stsp_latlon_in_desc_size", ()))
+TRANSFER_DESCRIPTOR = ("stsp_transfer_launch", [_CI, _P(TransferDesc), _VP], TransferDesc,
+                       ("stsp_transfer_desc_size", ()))
 
 
 def lib_path() -> str:
@@ -239,7 +252,7 @@ def load(build_if_missing: bool = True):
         L.stsp_fused_record_words.restype = ci
         L.stsp_fused_prime_launch.argtypes = [ci, vp, ci, vp, vp, ci, vp, ci, ci, vp]
         L.stsp_fused_prime_launch.restype = ci
-        for launch, argtypes, cls, (query, args) in DESCRIPTORS + [GRAD_DESCRIPTOR, LATLON_IN_DESCRIPTOR]:
+        for launch, argtypes, cls, (query, args) in DESCRIPTORS + [GRAD_DESCRIPTOR, LATLON_IN_DESCRIPTOR, TRANSFER_DESCRIPTOR]:
             fn, size = getattr(L, launch), getattr(L, query)
             fn.argtypes, fn.restype = argtypes, ci
             size.argtypes, size.restype = [ci] * len(args), ci
