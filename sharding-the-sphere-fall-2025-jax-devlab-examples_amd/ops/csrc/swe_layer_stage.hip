@@ -18,12 +18,14 @@
 //   * the Rusanov speed of both layers is |v_k . m| + sqrt(g (h_0 + h_1)) of the
 //     cell averages, which bounds the external and the internal wave speeds.
 //
-// Roles and tables are those of swe_tracer_stage.hip: thread e is edge e
-// (x-edges, then y-edges), thread o < BX BY loads and updates own cell o, the
-// next threads load one cell each of the two-cell ring around the block; the
-// panel-edge fix-up runs block-wide, one (field, side, strip cell) per thread
-// and pass.  Push map, carried corner ghosts (cpush / cgmap), partial blocks
-// and the block_sides rule are those of stage_kernel.hip.  No xGMI, no stamps.
+// Thread e is edge e (x-edges, then y-edges), thread o < BX BY loads and
+// updates own cell o, the next threads load one cell each of the two-cell ring
+// around the block; the panel-edge fix-up runs block-wide, one (field, side,
+// strip cell) per thread and pass.  Push map, carried corner ghosts (cpush /
+// cgmap) and partial blocks are those of stage_kernel.hip.  The geometry
+// constants, the block decode, the block_sides rule and the thread's window
+// cell are block_map.h, the argument check and the launch forms block_stage.h,
+// shared with swe_tracer_stage.hip and swe_layers_stream.hip.  No xGMI, no stamps.
 //
 // LDS (dynamic): the window holds the eight primitives and one sqrt(g H) row
 // shared by both layers.  The layers go through the five flux rows one after
@@ -37,26 +39,18 @@
 // 16x16 fp64: 65 360 bytes, under the 64 KiB a launch gets without opting in
 // (a plain copy of the tracer layout with eight resident fields: about 66 KB);
 // 16x8 fp64: 40 400.
-#include "stage_common.h"
+#include "block_stage.h"
 
 namespace {
 
 constexpr int LY_F = 8;      // state fields: (h, M) of two layers
 constexpr int LY_NG = 2;     // ghost layers (PLR)
 
-template <int BX, int BY> struct LyGeom {
-  static constexpr int NG = LY_NG;
-  static constexpr int NX = (BX + 1) * BY, NY = BX * (BY + 1), NE = NX + NY;
-  static constexpr int NT = ((NE + 63) / 64) * 64;
-  static constexpr int EX = BX + 2 * NG, EY = BY + 2 * NG;
-  static constexpr int WS = EX + 1, WF = EY * WS;      // window row / field stride
-  static constexpr int BM = BX > BY ? BX : BY, EM = EX > EY ? EX : EY;
-  static constexpr int NB = BX + BY + 2;               // normals: x columns, then y rows
-  static constexpr int FLR = 5;                        // flux rows: F_h, F_M, cbar_face of one layer
+template <int BX, int BY> struct LyGeom : BlockGeom<BX, BY, LY_NG> {
+  using B = BlockGeom<BX, BY, LY_NG>;
+  using B::WF; using B::NE; using B::BM; using B::NB; using B::EM; using B::FLR;   // FLR: F_h, F_M, cbar_face of one layer
   // window (h, v of both layers, sqrt(g H)) | flux rows | neighbour edge state | neighbour raw cell | normals | lengths
   static constexpr int ELEMS = (LY_F + 1) * WF + FLR * NE + LY_F * 4 * BM + LY_F * 4 * BM + 3 * NB + NE;
-  static_assert(EX * EY <= NT, "one window cell per thread");
-  static_assert(3 * NB <= NT, "one normal component per thread");
   static_assert(4 * LY_F * EM <= FLR * NE, "the raw strip copy fits in the flux array");
 };
 
@@ -77,19 +71,13 @@ __global__ __launch_bounds__((LyGeom<BX, BY>::NT)) __attribute__((amdgpu_waves_p
 
   const int bid = LIST ? a.blocks[blockIdx.x] : xcd_remap(blockIdx.x, a.nblocks);
   const int n = a.n, S = a.S, nn = n * n, mg = a.mg, pw = a.pw;
-  const int nbx = (n + BX - 1) / BX, nby = (n + BY - 1) / BY;
-  const int tile = bid / (nbx * nby);
-  const int rem = bid - tile * nbx * nby;
-  const int yb = rem / nbx, xb = rem - yb * nbx;
-  const int x0 = xb * BX, y0 = yb * BY;
+  const BlockPos bp = G::decode(bid, n);
+  const int tile = bp.tile, x0 = bp.x0, y0 = bp.y0;
   const int tid = threadIdx.x;
   const long tb = (long)tile * pw * pw;
   const int gbase = tile * nn;
   const int pe_word = a.pedge[tile];
-  // sides of this block on a cube edge: a side counts as soon as the window
-  // reaches its ghost strip (the last block may be one cell wide)
-  const int bsides = (x0 == 0 ? (pe_word & 1) : 0) | (x0 + BX + NG > n ? (pe_word & 2) : 0) |
-                     (y0 == 0 ? (pe_word & 4) : 0) | (y0 + BY + NG > n ? (pe_word & 8) : 0);
+  const int bsides = G::block_sides(pe_word, x0, y0, n);
 
   // ---- 0. own cell operands ---------------------------------------------------
   const int ox = tid % BX, oy = tid / BX;
@@ -153,21 +141,10 @@ __global__ __launch_bounds__((LyGeom<BX, BY>::NT)) __attribute__((amdgpu_waves_p
 
   // ---- 1. window (block + 2 ghost layers) -> LDS as primitives ------------------
   // Thread o < BX BY loads its own cell (and keeps the conserved values for the
-  // update), the next RING threads one cell each of the two-cell ring around
+  // update), the next threads one cell each of the two-cell ring around
   // the block: NG rows below and above, then NG columns left and right.
-  constexpr int NIN = BX * BY, RING = EX * EY - NIN;
-  int ly = -1, lx = 0;
-  if (tid < NIN) {
-    ly = NG + oy; lx = NG + ox;
-  } else if (tid - NIN < 2 * NG * EX) {
-    const int r = tid - NIN, rw = r / EX;
-    lx = r - rw * EX;
-    ly = rw < NG ? rw : EY - 2 * NG + rw;
-  } else if (tid - NIN < RING) {
-    const int q2 = tid - NIN - 2 * NG * EX, rw = q2 / (2 * NG), c = q2 - rw * (2 * NG);
-    ly = NG + rw;
-    lx = c < NG ? c : EX - 2 * NG + c;
-  }
+  int ly, lx;
+  G::window_cell(tid, ly, lx);
   if (ly >= 0) {
     const int x = x0 + lx - NG, y = y0 + ly - NG;
     T v[FR];
@@ -347,8 +324,8 @@ __global__ __launch_bounds__((LyGeom<BX, BY>::NT)) __attribute__((amdgpu_waves_p
       if (need_acc) acs1[f] = a.acc_in[(long)(4 + f) * S + pc];
     }
   }
-  const int ew = oy * (BX + 1) + ox;            // west x-edge of the cell
-  const int es = NX + oy * BX + ox;             // south y-edge
+  const int ew = G::west_edge(ox, oy);           // west x-edge of the cell
+  const int es = G::south_edge(ox, oy);          // south y-edge
   T Lw = T(0), Le = T(0), Ls = T(0), Ln = T(0);
   if (own) { Lw = s_len[ew]; Le = s_len[ew + 1]; Ls = s_len[es]; Ln = s_len[es + BX]; }
   // own-cell terms of one layer that need no flux: Coriolis, curvature balance
@@ -451,26 +428,14 @@ int ly_launch_l(const StageDesc* d, hipStream_t s) {
   const Args<T> a = make_args<T>(d);
   const T rr = (T)d->layer_r;
   const size_t lds = (size_t)G::ELEMS * sizeof(T);
-  if (lds > 65536) return -13;
-  const dim3 grid(d->nblocks), block(G::NT);
-  if (d->remote)
-    hipLaunchKernelGGL((swe_layer_kernel<T, BX, BY, LIM, true, true>), grid, block, lds, s, a, rr);
-  else if (d->blocks)
-    hipLaunchKernelGGL((swe_layer_kernel<T, BX, BY, LIM, false, true>), grid, block, lds, s, a, rr);
-  else
-    hipLaunchKernelGGL((swe_layer_kernel<T, BX, BY, LIM, false, false>), grid, block, lds, s, a, rr);
-  return (int)hipGetLastError();
+  return block_launch(d, swe_layer_kernel<T, BX, BY, LIM, true, true>, swe_layer_kernel<T, BX, BY, LIM, false, true>, swe_layer_kernel<T, BX, BY, LIM, false, false>, G::NT, lds, s, a, rr);
 }
 
 template <typename T, int BX, int BY>
 int ly_launch_t(const StageDesc* d, hipStream_t s) {
   if (d->nblocks <= 0) return 0;
   if (!(d->layer_r > 0.0 && d->layer_r <= 1.0)) return -17;           // densities increase downwards
-  if (d->pw != d->n + 2 * d->mg || d->mg < LY_NG) return -5;
-  if (!d->pedge || !d->pe_base || !d->pe_t || d->n < 2) return -12;   // panel-edge tables
-  if (!d->mx || !d->my || !d->cgeo || !d->ex || !d->ey) return -6;
-  if (!d->push || (d->remote && (!d->gmap || !d->blocks || !d->recv))) return -6;
-  if (d->xg) return -10;                                               // no direct xGMI halo
+  if (const int rc = block_args_check(d, LY_NG)) return rc;
   switch (d->limiter) {
     case 0: return ly_launch_l<T, BX, BY, 0>(d, s);
     case 1: return ly_launch_l<T, BX, BY, 1>(d, s);

@@ -2,8 +2,10 @@
 // launch, gfx950 (CDNA4).  models/swe.py::LayeredShallowWater is the twin; two
 // layers stay on swe_layer_stage.hip, whose roles, tables, panel-edge fix-up,
 // push map, carried corner ghosts, partial blocks and block_sides rule this
-// kernel keeps.  L is a launch value: the state (h_0, M_0, .., h_{L-1}, M_{L-1})
-// and the receive buffer are strided by 4 L.
+// kernel keeps (geometry constants, block decode, block_sides and the window
+// cell are block_map.h, the argument check and the launch forms block_stage.h).
+// L is a launch value: the state (h_0, M_0, .., h_{L-1}, M_{L-1}) and the
+// receive buffer are strided by 4 L.
 //
 // What differs is how a block walks the stack: it streams the layers through a
 // window sized for ONE layer, so its LDS does not depend on L.
@@ -48,27 +50,19 @@
 // way; 16x8 runs two blocks per CU rather than three.  fp32: 104 to 105, four.
 // Known cost: every h_j is read twice per stage.  Pass A prefetches h_{j+1}
 // under layer j's barriers.
-#include "stage_common.h"
+#include "block_stage.h"
 
 namespace {
 
 constexpr int LS_NG = 2;       // ghost layers (PLR)
 constexpr int LS_MIN = 3, LS_MAX = 8;
 
-template <int BX, int BY> struct LsGeom {
-  static constexpr int NG = LS_NG;
-  static constexpr int NX = (BX + 1) * BY, NY = BX * (BY + 1), NE = NX + NY;
-  static constexpr int NT = ((NE + 63) / 64) * 64;
-  static constexpr int EX = BX + 2 * NG, EY = BY + 2 * NG;
-  static constexpr int WS = EX + 1, WF = EY * WS;      // window row / field stride
-  static constexpr int BM = BX > BY ? BX : BY, EM = EX > EY ? EX : EY;
-  static constexpr int NB = BX + BY + 2;               // normals: x columns, then y rows
-  static constexpr int FLR = 5;                        // flux rows: F_h, F_M, cbar_face of one layer
+template <int BX, int BY> struct LsGeom : BlockGeom<BX, BY, LS_NG> {
+  using B = BlockGeom<BX, BY, LS_NG>;
+  using B::WF; using B::NE; using B::BM; using B::NB; using B::EM; using B::FLR;   // FLR: F_h, F_M, cbar_face of one layer
   // window (h, v of one layer, sqrt(g H)) | flux rows | neighbour edge state | neighbour raw cell | raw strips |
   // normals | lengths
   static constexpr int ELEMS = 5 * WF + FLR * NE + 4 * 4 * BM + 4 * 4 * BM + 4 * 4 * EM + 3 * NB + NE;
-  static_assert(EX * EY <= NT, "one window cell per thread");
-  static_assert(3 * NB <= NT, "one normal component per thread");
 };
 
 template <typename T, int BX, int BY, int LIM, bool REMOTE, bool LIST>
@@ -90,19 +84,13 @@ __global__ __launch_bounds__((LsGeom<BX, BY>::NT)) __attribute__((amdgpu_waves_p
   const int bid = LIST ? a.blocks[blockIdx.x] : xcd_remap(blockIdx.x, a.nblocks);
   const int n = a.n, S = a.S, nn = n * n, mg = a.mg, pw = a.pw;
   const int FR = 4 * nl;                          // fields of the state and of a receive-buffer row
-  const int nbx = (n + BX - 1) / BX, nby = (n + BY - 1) / BY;
-  const int tile = bid / (nbx * nby);
-  const int rem = bid - tile * nbx * nby;
-  const int yb = rem / nbx, xb = rem - yb * nbx;
-  const int x0 = xb * BX, y0 = yb * BY;
+  const BlockPos bp = G::decode(bid, n);
+  const int tile = bp.tile, x0 = bp.x0, y0 = bp.y0;
   const int tid = threadIdx.x;
   const long tb = (long)tile * pw * pw;
   const int gbase = tile * nn;
   const int pe_word = a.pedge[tile];
-  // sides of this block on a cube edge: a side counts as soon as the window
-  // reaches its ghost strip (the last block may be one cell wide)
-  const int bsides = (x0 == 0 ? (pe_word & 1) : 0) | (x0 + BX + NG > n ? (pe_word & 2) : 0) |
-                     (y0 == 0 ? (pe_word & 4) : 0) | (y0 + BY + NG > n ? (pe_word & 8) : 0);
+  const int bsides = G::block_sides(pe_word, x0, y0, n);
 
   // ---- 0. own cell operands ---------------------------------------------------
   const int ox = tid % BX, oy = tid / BX;
@@ -167,22 +155,11 @@ __global__ __launch_bounds__((LsGeom<BX, BY>::NT)) __attribute__((amdgpu_waves_p
   const int cst = is_x ? 1 : WS;
 
   // ---- 1. this thread's window cell: where every layer's values come from --------
-  // Thread o < BX BY loads its own cell, the next RING threads one cell each of
+  // Thread o < BX BY loads its own cell, the next threads one cell each of
   // the two-cell ring around the block: NG rows below and above, then NG
   // columns left and right.  Field f of the state is lp[lbase + f * lstr].
-  constexpr int NIN = BX * BY, RING = EX * EY - NIN;
-  int ly = -1, lx = 0;
-  if (tid < NIN) {
-    ly = NG + oy; lx = NG + ox;
-  } else if (tid - NIN < 2 * NG * EX) {
-    const int r = tid - NIN, rw = r / EX;
-    lx = r - rw * EX;
-    ly = rw < NG ? rw : EY - 2 * NG + rw;
-  } else if (tid - NIN < RING) {
-    const int q2 = tid - NIN - 2 * NG * EX, rw = q2 / (2 * NG), c = q2 - rw * (2 * NG);
-    ly = NG + rw;
-    lx = c < NG ? c : EX - 2 * NG + c;
-  }
+  int ly, lx;
+  G::window_cell(tid, ly, lx);
   const int wi = ly * WS + lx;
   const T* lp = nullptr;           // null: no window cell, or one past a partial block (zeros)
   long lbase = 0, lstr = 0;
@@ -295,8 +272,8 @@ __global__ __launch_bounds__((LsGeom<BX, BY>::NT)) __attribute__((amdgpu_waves_p
   const T snb = tsqrt(a.g * tmax(hnb, T(0)));   // the neighbour's raw sound speed at a panel edge
 
   // ---- 3. pass B: one layer at a time through the window --------------------------
-  const int ew = oy * (BX + 1) + ox;            // west x-edge of the cell
-  const int es = NX + oy * BX + ox;             // south y-edge
+  const int ew = G::west_edge(ox, oy);           // west x-edge of the cell
+  const int es = G::south_edge(ox, oy);          // south y-edge
   const int ni = is_x ? e_c : BX + 1 + e_r;
   for (int k = 0; k < nl; ++k) {
     const int fo = 4 * k;
@@ -450,15 +427,7 @@ int ls_launch_l(const StageDesc* d, hipStream_t s) {
   const Args<T> a = make_args<T>(d);
   const T rr = (T)d->layer_r;
   const size_t lds = (size_t)G::ELEMS * sizeof(T);
-  if (lds > 65536) return -13;
-  const dim3 grid(d->nblocks), block(G::NT);
-  if (d->remote)
-    hipLaunchKernelGGL((swe_layers_stream_kernel<T, BX, BY, LIM, true, true>), grid, block, lds, s, a, rr, d->layers);
-  else if (d->blocks)
-    hipLaunchKernelGGL((swe_layers_stream_kernel<T, BX, BY, LIM, false, true>), grid, block, lds, s, a, rr, d->layers);
-  else
-    hipLaunchKernelGGL((swe_layers_stream_kernel<T, BX, BY, LIM, false, false>), grid, block, lds, s, a, rr, d->layers);
-  return (int)hipGetLastError();
+  return block_launch(d, swe_layers_stream_kernel<T, BX, BY, LIM, true, true>, swe_layers_stream_kernel<T, BX, BY, LIM, false, true>, swe_layers_stream_kernel<T, BX, BY, LIM, false, false>, G::NT, lds, s, a, rr, (int)d->layers);
 }
 
 template <typename T, int BX, int BY>
@@ -466,11 +435,7 @@ int ls_launch_t(const StageDesc* d, hipStream_t s) {
   if (d->nblocks <= 0) return 0;
   if (d->layers < LS_MIN || d->layers > LS_MAX) return -18;            // two layers: swe_layer_stage.hip
   if (!(d->layer_r > 0.0 && d->layer_r <= 1.0)) return -17;           // densities increase downwards
-  if (d->pw != d->n + 2 * d->mg || d->mg < LS_NG) return -5;
-  if (!d->pedge || !d->pe_base || !d->pe_t || d->n < 2) return -12;   // panel-edge tables
-  if (!d->mx || !d->my || !d->cgeo || !d->ex || !d->ey) return -6;
-  if (!d->push || (d->remote && (!d->gmap || !d->blocks || !d->recv))) return -6;
-  if (d->xg) return -10;                                               // no direct xGMI halo
+  if (const int rc = block_args_check(d, LS_NG)) return rc;
   switch (d->limiter) {
     case 0: return ls_launch_l<T, BX, BY, 0>(d, s);
     case 1: return ls_launch_l<T, BX, BY, 1>(d, s);

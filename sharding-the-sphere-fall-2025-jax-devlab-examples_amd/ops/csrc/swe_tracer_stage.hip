@@ -14,8 +14,11 @@
 // updates own cell o, the next threads load one cell each of the two-cell ring
 // around the block; the panel-edge
 // fix-up runs block-wide, one (field, side, strip cell) per thread and pass.
-// Push map, carried corner ghosts (cpush / cgmap), partial blocks and the
-// block_sides rule are those of stage_kernel.hip.  No xGMI, no stamps.
+// Push map, carried corner ghosts (cpush / cgmap) and partial blocks are those
+// of stage_kernel.hip.  The geometry constants, the block decode, the
+// block_sides rule and the thread's window cell are block_map.h, the argument
+// check and the launch forms block_stage.h, shared with swe_layer_stage.hip and
+// swe_layers_stream.hip.  No xGMI, no stamps.
 //
 // TLIM, the tracers' reconstruction, is "same as LIM" (0) or the monotone PPM
 // (4, ShallowWaterTracers(tracer_limiter="ppm")): the mixing ratios alone go
@@ -35,7 +38,7 @@
 // once the momentum fluxes are consumed.  16x16 fp64 with NQ = 4: 63 824 bytes,
 // under the 64 KiB a launch gets without opting in; with PPM tracers 70 016
 // bytes, which the launcher refuses (NQ <= 3: 65 456; 16x8 with NQ = 4: 43 904).
-#include "stage_common.h"
+#include "block_stage.h"
 
 namespace {
 
@@ -45,20 +48,13 @@ constexpr int tr_ng(int tlim) { return tlim == TR_PPM ? 3 : 2; }   // ghost laye
 
 // NG ghost layers; the fix-up interpolates layer 0 of every field and, with
 // NG = 3, layer 1 of the tracer rows
-template <int BX, int BY, int NG> struct TrGeom {
-  static constexpr int NX = (BX + 1) * BY, NY = BX * (BY + 1), NE = NX + NY;
-  static constexpr int NT = ((NE + 63) / 64) * 64;
-  static constexpr int EX = BX + 2 * NG, EY = BY + 2 * NG;
-  static constexpr int WS = EX + 1, WF = EY * WS;      // window row / field stride
-  static constexpr int BM = BX > BY ? BX : BY, EM = EX > EY ? EX : EY;
-  static constexpr int NB = BX + BY + 2;               // normals: x columns, then y rows
-  static constexpr int FLR = 5;                        // flux rows
+template <int BX, int BY, int NG> struct TrGeom : BlockGeom<BX, BY, NG> {
+  using B = BlockGeom<BX, BY, NG>;
+  using B::WF; using B::NE; using B::BM; using B::NB; using B::EM; using B::FLR;
   // window (h, v, c, q_k) | fluxes | neighbour edge state | neighbour raw cell | normals | lengths
   static constexpr int elems(int nq) {
     return (5 + nq) * WF + FLR * NE + (4 + nq) * 4 * BM + 5 * 4 * BM + 3 * NB + NE;
   }
-  static_assert(EX * EY <= NT, "one window cell per thread");
-  static_assert(3 * NB <= NT, "one normal component per thread");
   // raw strip copy: layer 0 of all 4 + NQ fields, layer 1 of the NQ tracer rows (NG = 3)
   static constexpr int raw_rows(int nq) { return 4 + nq + (NG == 3 ? nq : 0); }
   static_assert(4 * raw_rows(TR_MAXQ) * EM <= FLR * NE, "the raw strip copy fits in the flux array");
@@ -107,19 +103,13 @@ __global__ __launch_bounds__((TrGeom<BX, BY, tr_ng(TLIM)>::NT)) void swe_tracer_
 
   const int bid = LIST ? a.blocks[blockIdx.x] : xcd_remap(blockIdx.x, a.nblocks);
   const int n = a.n, S = a.S, nn = n * n, mg = a.mg, pw = a.pw;
-  const int nbx = (n + BX - 1) / BX, nby = (n + BY - 1) / BY;
-  const int tile = bid / (nbx * nby);
-  const int rem = bid - tile * nbx * nby;
-  const int yb = rem / nbx, xb = rem - yb * nbx;
-  const int x0 = xb * BX, y0 = yb * BY;
+  const BlockPos bp = G::decode(bid, n);
+  const int tile = bp.tile, x0 = bp.x0, y0 = bp.y0;
   const int tid = threadIdx.x;
   const long tb = (long)tile * pw * pw;
   const int gbase = tile * nn;
   const int pe_word = a.pedge[tile];
-  // sides of this block on a cube edge: a side counts as soon as the window
-  // reaches its ghost strip (the last block may be one cell wide)
-  const int bsides = (x0 == 0 ? (pe_word & 1) : 0) | (x0 + BX + NG > n ? (pe_word & 2) : 0) |
-                     (y0 == 0 ? (pe_word & 4) : 0) | (y0 + BY + NG > n ? (pe_word & 8) : 0);
+  const int bsides = G::block_sides(pe_word, x0, y0, n);
 
   // ---- 0. own cell operands ---------------------------------------------------
   const int ox = tid % BX, oy = tid / BX;
@@ -187,21 +177,10 @@ __global__ __launch_bounds__((TrGeom<BX, BY, tr_ng(TLIM)>::NT)) void swe_tracer_
 
   // ---- 1. window (block + 2 ghost layers) -> LDS as primitives ------------------
   // Thread o < BX BY loads its own cell (and keeps the conserved values for the
-  // update), the next RING threads one cell each of the two-cell ring around
+  // update), the next threads one cell each of the two-cell ring around
   // the block: NG rows below and above, then NG columns left and right.
-  constexpr int NIN = BX * BY, RING = EX * EY - NIN;
-  int ly = -1, lx = 0;
-  if (tid < NIN) {
-    ly = NG + oy; lx = NG + ox;
-  } else if (tid - NIN < 2 * NG * EX) {
-    const int r = tid - NIN, rr = r / EX;
-    lx = r - rr * EX;
-    ly = rr < NG ? rr : EY - 2 * NG + rr;
-  } else if (tid - NIN < RING) {
-    const int r2 = tid - NIN - 2 * NG * EX, rr = r2 / (2 * NG), c = r2 - rr * (2 * NG);
-    ly = NG + rr;
-    lx = c < NG ? c : EX - 2 * NG + c;
-  }
+  int ly, lx;
+  G::window_cell(tid, ly, lx);
   if (ly >= 0) {
     const int x = x0 + lx - NG, y = y0 + ly - NG;
     T v[4] = {T(0), T(0), T(0), T(0)}, tq[TR_MAXQ] = {T(0), T(0), T(0), T(0)};
@@ -433,8 +412,8 @@ __global__ __launch_bounds__((TrGeom<BX, BY, tr_ng(TLIM)>::NT)) void swe_tracer_
     }
   }
   // own-cell terms that need no flux: sources and the RK base
-  const int ew = oy * (BX + 1) + ox;            // west x-edge of the cell
-  const int es = NX + oy * BX + ox;             // south y-edge
+  const int ew = G::west_edge(ox, oy);           // west x-edge of the cell
+  const int es = G::south_edge(ox, oy);          // south y-edge
   T src[3] = {T(0), T(0), T(0)};
   if (own) {
     const T fc = a.omega2 * r2;
@@ -541,27 +520,16 @@ int tr_launch_l(const StageDesc* d, hipStream_t s) {
   const Args<T> a = make_args<T>(d);
   const int nq = d->nq;
   const size_t lds = (size_t)G::elems(nq) * sizeof(T);
-  if (lds > 65536) return -13;
-  const dim3 grid(d->nblocks), block(G::NT);
-  if (d->remote)
-    hipLaunchKernelGGL((swe_tracer_kernel<T, BX, BY, LIM, TLIM, true, true>), grid, block, lds, s, a, nq);
-  else if (d->blocks)
-    hipLaunchKernelGGL((swe_tracer_kernel<T, BX, BY, LIM, TLIM, false, true>), grid, block, lds, s, a, nq);
-  else
-    hipLaunchKernelGGL((swe_tracer_kernel<T, BX, BY, LIM, TLIM, false, false>), grid, block, lds, s, a, nq);
-  return (int)hipGetLastError();
+  return block_launch(d, swe_tracer_kernel<T, BX, BY, LIM, TLIM, true, true>, swe_tracer_kernel<T, BX, BY, LIM, TLIM, false, true>, swe_tracer_kernel<T, BX, BY, LIM, TLIM, false, false>, G::NT, lds, s, a, nq);
 }
 
 template <typename T, int BX, int BY, int TLIM>
 int tr_launch_t(const StageDesc* d, hipStream_t s) {
   if (d->nblocks <= 0) return 0;
   if (d->nq < 1 || d->nq > TR_MAXQ) return -14;
-  if (d->pw != d->n + 2 * d->mg || d->mg < 2) return -5;
-  if (d->mg < tr_ng(TLIM)) return -15;                                 // PPM tracers: three ghost layers
-  if (!d->pedge || !d->pe_base || !d->pe_t || d->n < 2) return -12;   // panel-edge tables
-  if (!d->mx || !d->my || !d->cgeo || !d->ex || !d->ey) return -6;
-  if (!d->push || (d->remote && (!d->gmap || !d->blocks || !d->recv))) return -6;
-  if (d->xg) return -10;                                               // no direct xGMI halo
+  const int rc = block_args_check(d, tr_ng(0));
+  if (rc != -5 && d->mg < tr_ng(TLIM)) return -15;                     // PPM tracers: three ghost layers (after -5 only)
+  if (rc) return rc;
   switch (d->limiter) {
     case 0: return tr_launch_l<T, BX, BY, 0, TLIM>(d, s);
     case 1: return tr_launch_l<T, BX, BY, 1, TLIM>(d, s);
