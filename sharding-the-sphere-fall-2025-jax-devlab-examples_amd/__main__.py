@@ -21,6 +21,10 @@
     spectrum HISTORY.zarr FIELD LMAX OUT.npz           power per degree 0 .. LMAX of a history field (``ke``:
                                                        the kinetic-energy spectrum of a shallow-water
                                                        history), on the CPU
+    eof HISTORY.zarr FIELD K OUT.npz [--first I] [--last J] [--stride S]
+                                                       the leading K snapshot EOFs of a history field over its
+                                                       frames I .. J (at most 64; --stride thins them): values,
+                                                       fraction, patterns, pcs, mean and the frame indices
     synth HISTORY.zarr FIELD LMAX OUT.npz [--band LMIN LCUT]
                                                        a history field analysed to degree LMAX and synthesised
                                                        back on the cells (--band: degrees LMIN .. LCUT only), or
@@ -91,6 +95,14 @@ def main(argv=None):
     sp.add_argument("field")
     sp.add_argument("lmax", type=int)
     sp.add_argument("out")
+    eo = sub.add_parser("eof")
+    eo.add_argument("history")
+    eo.add_argument("field")
+    eo.add_argument("k", type=int)
+    eo.add_argument("out")
+    eo.add_argument("--first", type=int, default=0)
+    eo.add_argument("--last", type=int, default=None, help="the last frame taken (default: the history's last)")
+    eo.add_argument("--stride", type=int, default=1)
     sy = sub.add_parser("synth")
     sy.add_argument("history")
     sy.add_argument("field")
@@ -176,6 +188,13 @@ def main(argv=None):
         r = spectrum_history(a.history, a.field, a.lmax)
         np.savez(a.out, **r)
         print(json.dumps({"out": a.out, "field": a.field, "shape": list(r["spectrum"].shape)}))
+        return 0
+    if a.cmd == "eof":
+        import numpy as np
+        r = eof_history(a.history, a.field, a.k, a.first, a.last, a.stride)
+        np.savez(a.out, **r)
+        print(json.dumps({"out": a.out, "field": a.field, "frames": len(r["frames"]),
+                          "fraction": [float(v) for v in r["fraction"]]}))
         return 0
     if a.cmd == "synth":
         import numpy as np
@@ -405,6 +424,37 @@ def spectrum_history(history: str, field: str, lmax: int) -> dict:
             out.append(ms.power(ms.analyse(fr.reshape(1, -1), tb))[0])
     return {"spectrum": torch.stack(out).numpy(), "degree": np.arange(lmax + 1),
             "time": zarr_lite.read_array(history, "time")}
+
+
+def eof_history(history: str, field: str, k: int, first: int = 0, last=None, stride: int = 1) -> dict:
+    """The leading ``k`` snapshot EOFs of a history field over its frames
+    ``first``, ``first + stride``, .. <= ``last`` (``Solver.eofs`` of a one-rank
+    solver on the history's grid: the kernel with the HIP backend on a GPU, the
+    twin otherwise), with the frame indices as ``frames``."""
+    import numpy as np
+    from .models.eof import MAX_S
+    from .utils import zarr_lite
+    have = zarr_lite.list_arrays(history)
+    if field not in have:
+        raise ValueError(f"{history}: no array {field!r} (it holds {[f for f in have if f not in ('time', 'step')]})")
+    src = zarr_lite.read_array(history, field)                                  # [frames, 6, N, N]
+    if stride < 1:
+        raise ValueError(f"eof: --stride {stride} is not a positive step")
+    idx = np.arange(len(src))[first:(None if last is None else last + 1):stride]
+    if len(idx) > MAX_S:
+        raise ValueError(f"eof: {len(idx)} frames chosen, at most {MAX_S} are taken; thin them with --stride")
+    import torch
+    cfg = dict(zarr_lite.read_attrs(history).get("config") or {})
+    cfg["parallelization"] = {"num_devices": 1, "tiles_per_edge": 1,
+                              "device_type": "gpu" if torch.cuda.is_available() else "cpu"}
+    cfg["io"] = {}
+    from .driver import Solver
+    s = Solver(cfg, verbose=False)
+    s.initialize()
+    r = s.eofs(np.ascontiguousarray(src[idx], dtype=np.float64), k)
+    s.close()
+    r["frames"] = idx
+    return r
 
 
 def synth_history(history: str, field: str, lmax: int, band=None) -> dict:

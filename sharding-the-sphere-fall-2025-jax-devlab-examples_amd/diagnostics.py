@@ -296,6 +296,43 @@ class SolverDiagnostics:
         x, self.helmholtz_record = e.heat_operator().solve(b, tau, tol=tol, maxiter=maxiter)
         return self._gather_tiles({e.rank: x.detach().cpu().numpy()})
 
+    def eofs(self, frames, k: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """Snapshot EOFs (models/eof.py) of ``frames`` [S, 6, N, N] on the solver's grid
+        (numpy or torch; history frames of one field are the use case), 2 <= S <= 64:
+        ``values`` [k], ``fraction`` [k], ``total``, ``patterns`` [k, 6, N, N], ``pcs``
+        [k, S] and ``mean`` [6, N, N], float64 on the host.  ``k`` defaults to
+        min(S-1, 8).  With the HIP backend on a GPU ops/csrc/eof_kernel.hip runs on the
+        contiguous snapshots (``ops.eof.Eof``, kept per (S, k)); otherwise the twin.
+        One rank."""
+        from .models import eof as me
+        if self.mode != "single":
+            raise ValueError("eof: one rank only (the Gram matrix would need a fold across ranks)")
+        e = self.engines[0]
+        f = frames.detach().cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+        N = self.layout.N
+        if f.ndim != 4 or f.shape[1:] != (6, N, N):
+            raise ValueError(f"eof: frames of shape [S, 6, {N}, {N}] expected, not {f.shape}")
+        k = me.check_args(f.shape[0], k)
+        if f.dtype not in (np.float32, np.float64):
+            f = f.astype(np.float64)
+        x = torch.as_tensor(np.ascontiguousarray(np.moveaxis(e.geo.gather_global(np.moveaxis(f, 0, -1)), -1, 0)),
+                            device=e.device)
+        if e.backend == "hip" and e.device.type == "cuda":
+            from .ops.eof import Eof
+            cache = self.__dict__.setdefault("_eofs", {})
+            key = (f.shape[0], k)
+            if key not in cache:
+                cache.clear()
+                cache[key] = Eof(e, f.shape[0], k, padded=False)
+            r = cache[key].compute(x)
+        else:
+            r = me.eofs(x, torch.as_tensor(e.geo.area, device=e.device), k)
+        out = {name: r[name].detach().cpu().numpy() for name in ("values", "fraction", "pcs")}
+        out["total"] = float(r["total"])
+        out["patterns"] = self._gather_tiles({e.rank: r["patterns"].detach().cpu().numpy()})
+        out["mean"] = self._gather_tiles({e.rank: r["mean"].detach().cpu().numpy()})
+        return out
+
     # ---- lat-lon output (models/latlon.py, ops/latlon.py) ---------------------------
     def latlon_names(self) -> List[str]:
         """What ``latlon_field`` / ``zonal_mean`` accept for this model."""

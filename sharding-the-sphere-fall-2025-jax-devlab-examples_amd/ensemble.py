@@ -129,6 +129,7 @@ class Ensemble:
         self._graph = None
         self._stats = None
         self._letkf = None
+        self._eofs = None
         phys0 = physics_factory()
         if getattr(phys0, "time_dependent", False):
             raise ValueError(f"an ensemble of a time-dependent physics ({phys0.name}, flow "
@@ -382,6 +383,28 @@ class Ensemble:
         from .models.ensemble_stats import ensemble_stats
         x = torch.stack([e.tiles_view()[field] for e in self.engines])      # [M, T, n, n]
         return ensemble_stats(x, e0.tens["area"].reshape(x.shape[1:]))
+
+    def eofs(self, field: int = 0, k: Optional[int] = None) -> dict:
+        """Snapshot EOFs of one field over the members (models/eof.py): the
+        leading ``k`` (default min(M-1, 8)) modes of the members' spread, as
+        ``values`` [k], ``fraction`` [k], ``total``, ``patterns`` [k, T, n, n],
+        ``pcs`` [k, M] and ``mean`` [T, n, n], float64 device tensors.  2 .. 64
+        members.  Batched mode on the HIP backend runs ops/csrc/eof_kernel.hip in
+        place on the batched state (the tensors are its buffers, overwritten by
+        the next call); every other setting stacks the members and runs the
+        twin."""
+        from .models import eof as me
+        e0 = self.engines[0]
+        k = me.check_args(self.members, k)
+        if not 0 <= int(field) < e0.physics.F:
+            raise ValueError(f"eof: field {field} of a state with {e0.physics.F} fields")
+        if self.mode == "batched" and self.native:
+            if self._eofs is None or self._eofs.k != k:
+                from .ops.eof import Eof
+                self._eofs = Eof(e0, self.members, k, padded=True)
+            return self._eofs.compute(self.batch[0], field)
+        x = torch.stack([e.tiles_view()[field] for e in self.engines])      # [M, T, n, n]
+        return me.eofs(x, torch.as_tensor(e0.geo.area, device=x.device), k)
 
     # ---- data assimilation ------------------------------------------------------
     def _sample_members(self, p: torch.Tensor, fields: torch.Tensor) -> torch.Tensor:

@@ -18,7 +18,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libstsp.so")
-SOURCES = ["stage_kernel.hip", "march_kernel.hip", "march3_kernel.hip", "swe_tracer_stage.hip", "swe_layer_stage.hip", "swe_layers_stream.hip", "fused_step.hip", "derived_kernel.hip", "dissipation_kernel.hip", "heat_kernel.hip", "helmholtz_kernel.hip", "wind_kernel.hip", "ensemble_kernel.hip", "letkf_kernel.hip", "latlon_kernel.hip", "latlon_in_kernel.hip", "transfer_kernel.hip", "points_kernel.hip", "spectra_kernel.hip", "synth_kernel.hip", "grad_synth_kernel.hip", "tt_kernels.hip", "tt_persist.hip", "runtime.cpp"]
+SOURCES = ["stage_kernel.hip", "march_kernel.hip", "march3_kernel.hip", "swe_tracer_stage.hip", "swe_layer_stage.hip", "swe_layers_stream.hip", "fused_step.hip", "derived_kernel.hip", "dissipation_kernel.hip", "heat_kernel.hip", "helmholtz_kernel.hip", "wind_kernel.hip", "ensemble_kernel.hip", "letkf_kernel.hip", "eof_kernel.hip", "latlon_kernel.hip", "latlon_in_kernel.hip", "transfer_kernel.hip", "points_kernel.hip", "spectra_kernel.hip", "synth_kernel.hip", "grad_synth_kernel.hip", "tt_kernels.hip", "tt_persist.hip", "runtime.cpp"]
 HEADERS = ["stsp_kernels.h", "stage_common.h", "block_map.h", "block_stage.h", "xg_ring.h", "xg_codec.h", "march_common.h", "tt_common.h", "runtime.h", "rccl_abi.h"]
 # extra compile flags of single sources: the layer-streaming kernel is built
 # without the packed fp32 instructions (v_pk_*_f32)

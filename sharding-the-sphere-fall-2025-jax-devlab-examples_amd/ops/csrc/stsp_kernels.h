@@ -590,6 +590,38 @@ typedef struct LetkfDesc {
 } LetkfDesc;
 int stsp_letkf_launch(int dtype, const LetkfDesc* d, hipStream_t stream);
 int stsp_letkf_desc_size(void);
+// Snapshot EOFs of S <= 64 snapshots over the cells (eof_kernel.hip, ops/eof.py;
+// definitions and the twin in models/eof.py): the weighted Gram matrix of the
+// anomalies per slab of 64-cell tiles on the fp64 matrix cores, a fold of the
+// slabs' partials in ascending order, one workgroup of cyclic Jacobi, and the
+// projection of the anomalies on the leading k modes.  Four ordinary launches.
+// Everything but X is float64.  err[0] is set to 1 when the Jacobi reaches its
+// sweep cap; the caller clears it before and reads it after the launch.
+#define STSP_EOF_MAX_S 64
+typedef struct EofDesc {
+  const void* X;        // snapshots (element type): [S][cells], or the batched state [M][F][Sp] (padded = 1)
+  const double* w;      // [cells] a_i = A_i / sum(A) in cell order ([T][n][n] when padded)
+  double* partials;     // [slabs][Spad][Spad] work (upper 16 x 16 tiles)
+  double* C;            // [Spad][Spad] out: the covariance (zero beyond S)
+  double* U;            // [Kpad][Spad] work: v_k / sqrt((S-1) lam_k), zero rows for zero modes
+  double* values;       // [k] out: lam, descending
+  double* total;        // [1] out: trace(C)
+  double* pcs;          // [k][S] out
+  double* patterns;     // [k][cells] out
+  double* mean;         // [cells] out
+  int* err;             // [1]
+  long long snap_stride;  // elements from one snapshot to the next (padded: the member stride)
+  int S, Spad;          // snapshots 2 .. 64, rounded up to 16
+  int k, Kpad;          // modes 1 .. S-1, rounded up to 16
+  int padded;           // 0: contiguous snapshots; 1: one field of a batched padded state
+  int cells;            // cells of a snapshot (padded: ntile n^2)
+  int fields, field;    // padded: fields of the state and the one taken
+  int ntile, n, Sp, mg, pw;  // padded: as StageDesc (Sp = ntile pw^2)
+  int slabs, slab_tiles;     // workgroups of the two tall passes; 64-cell tiles per slab
+} EofDesc;
+int stsp_eof_launch(int dtype, const EofDesc* d, hipStream_t stream);
+int stsp_eof_desc_size(void);
+int stsp_eof_eigen_lds(int S);   // dynamic LDS bytes of the Jacobi workgroup
 // Time-dependent winds of the advection model (wind_kernel.hip, ops/wind.py; the
 // twin: models/advection.py): one launch before a Runge-Kutta stage refills the
 // stage kernel's transport tables ex / ey in place at the stage time
